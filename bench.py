@@ -14,10 +14,14 @@ which the HIP path and the oracle take the same decisions (`parity_ok`).  The ze
 8-iteration schedule of rounds 1-5 (two cheap steps past convergence per solve) is reported beside
 it as `value_fixed8_schedule`, never as `value`.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]         (N > 1: spawns N ranks under torch.distributed.run itself)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                                                                (N > 1: spawns N ranks under torch.distributed.run itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel, the J*v product inside LSMR
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times ONE region of K steps and prints the headline (`value`,
+`ms_per_step`); --dump-outputs DIR also writes what the last timed solve returned (minimizer, residual, ssr, counts) as .npy
+files.  Everything below -- 25 timed regions (median), `roofline`, `cpu_baseline`, `parity_vs_cpu` and the companion legs --
+is measured with --full only (null otherwise).  `roofline` is for the dominant kernel, the J*v product inside LSMR
 (k_sell_rows<EpiU>): algorithmic bytes per launch (12*nnz + 4*(m+1) + 8*n + 16*m
 = 140.08 MB, plus 24*n for the fused damping rows) / average launch duration measured with HIP
 events on the library's stream inside the timed region.  `cpu_baseline` is the oracle (scalar C
@@ -52,8 +56,14 @@ def parse():
     ap.add_argument("--cpu-steps", type=int, default=96, help="outer iterations of the CPU baseline sample (0 = skip)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-dense", action="store_true", help="skip the secondary dense-path timings (C2/C3 ldiv!)")
-    ap.add_argument("--repeats", type=int, default=25,
-                    help="how many times the K-step timed region is repeated (value = median region)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="how many times the K-step timed region is repeated (value = median region; default 1, 25 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: 25 timed regions, the J*v / J'u launch timings (roofline), "
+                         "the CPU baseline and its parity check, the fixed-8 schedule, the generic g!, dense and wide-n legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed solve returned (minimizer, residual, ssr, counts) "
+                         "as DIR/<name>.npy in float64 (rank 0)")
     ap.add_argument("--exchange", choices=("rccl", "nccl", "gloo"), default=os.environ.get("LSQ_EXCHANGE_BACKEND", "rccl"),
                     help="the per-outer-iteration ||r|| exchange of sharded runs: rccl = served in C (liblsqrccl.so: a direct "
                          "ncclAllReduce over xGMI on a side stream, torch only carries the unique id); nccl / gloo = the "
@@ -225,16 +235,17 @@ def main():
     if a.warmup > 0:
         run(a.warmup)
     # The timed region is EXACTLY K steps between barrier + synchronize; it is repeated --repeats times (each
-    # repeat bracketed the same way) and `value` comes from the MEDIAN region, so the headline is not one sample
-    # of a few milliseconds.  Every twelfth J*v launch of every region carries its own start/stop events (250 samples
-    # per run; a timed launch costs ~9 us of pipeline gaps, so every third -- rounds 1-3 -- cost 1.5 % of the rate it measured).
+    # repeat bracketed the same way: once by default, 25 times with --full) and `value` comes from the MEDIAN region.
+    # --full: every twelfth J*v launch of every region carries its own start/stop events (250 samples per run; a timed
+    # launch costs ~9 us of pipeline gaps, so every third -- rounds 1-3 -- cost 1.5 % of the rate it measured).
     probe("warm-up done")
-    stride = int(os.environ.get("LSQ_BENCH_PROF_STRIDE", "12"))
-    L.lsq_prof_select(ctx.h, 1 | (stride << 8))     # bits 0-7: kernel mask; bits 8+: time every k-th launch
-    L.lsq_prof_begin(ctx.h, 1 << 16)
+    if a.full:
+        stride = int(os.environ.get("LSQ_BENCH_PROF_STRIDE", "12"))
+        L.lsq_prof_select(ctx.h, 1 | (stride << 8))     # bits 0-7: kernel mask; bits 8+: time every k-th launch
+        L.lsq_prof_begin(ctx.h, 1 << 16)
     region_s, inner_local, real_local, r = [], 0, 0, None
     tail_before = ctx.tail_stats()
-    reps = max(1, a.repeats)
+    reps = max(1, a.repeats if a.repeats is not None else (25 if a.full else 1))
     for _ in range(reps):
         barrier()
         t0 = time.perf_counter()
@@ -246,28 +257,34 @@ def main():
         assert steps_done == a.steps, (steps_done, a.steps)
         assert world > 1 or real_rep == a.steps, (real_rep, a.steps)
     tail_timed = tuple(int(x - y) for x, y in zip(ctx.tail_stats(), tail_before))
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last solve (the one that ended the last timed step)
+        dump_outputs(a.dump_outputs, {
+            "minimizer": pr.x.get(), "residual": pr.fcur.get(), "ssr": [r.ssr],
+            "counts": [r.iterations, r.f_calls, r.g_calls, r.mul_calls, r.lsmr_iterations, r.converged]})
     iters_per_ref_solve = None
-    if r is not None:
-        pr.reset()
-        iters_per_ref_solve = pr.optimize(LM, LSMR, iterations=SOLVE_CAP, allreduce=allreduce, fetch_x=False).iterations
-    probe("timed regions done")
-    avg = (C.c_double * 2)()
-    cnt = (C.c_int * 2)()
-    L.lsq_prof_end(ctx.h, avg, cnt)
-    probe("lsq_prof_end")
-    # the J'u kernel is timed in a separate (untimed) pass of one solve: every instrumented launch
-    # costs a few microseconds of pipeline gaps, which the timed region should not pay twice
-    L.lsq_prof_select(ctx.h, 2)
-    L.lsq_prof_begin(ctx.h, 8192)
-    run(a.iters_per_solve, fixed=a.iters_per_solve)
-    avg2 = (C.c_double * 2)()
-    cnt2 = (C.c_int * 2)()
-    L.lsq_prof_end(ctx.h, avg2, cnt2)
-    avg[1], cnt[1] = avg2[1], cnt2[1]
-    L.lsq_prof_select(ctx.h, 3)
-    ev_ovh = C.c_double(0.0)   # what an EMPTY event pair measures on this stream (marker overhead)
-    L.lsq_prof_overhead(ctx.h, 50, C.byref(ev_ovh))
-    probe("J'u pass + overhead")
+    if a.full:
+        if r is not None:
+            pr.reset()
+            iters_per_ref_solve = pr.optimize(LM, LSMR, iterations=SOLVE_CAP, allreduce=allreduce, fetch_x=False).iterations
+        probe("timed regions done")
+        avg = (C.c_double * 2)()
+        cnt = (C.c_int * 2)()
+        L.lsq_prof_end(ctx.h, avg, cnt)
+        probe("lsq_prof_end")
+        # the J'u kernel is timed in a separate (untimed) pass of one solve: every instrumented launch
+        # costs a few microseconds of pipeline gaps, which the timed region should not pay twice
+        L.lsq_prof_select(ctx.h, 2)
+        L.lsq_prof_begin(ctx.h, 8192)
+        run(a.iters_per_solve, fixed=a.iters_per_solve)
+        avg2 = (C.c_double * 2)()
+        cnt2 = (C.c_int * 2)()
+        L.lsq_prof_end(ctx.h, avg2, cnt2)
+        avg[1], cnt[1] = avg2[1], cnt2[1]
+        L.lsq_prof_select(ctx.h, 3)
+        ev_ovh = C.c_double(0.0)   # what an EMPTY event pair measures on this stream (marker overhead)
+        L.lsq_prof_overhead(ctx.h, 50, C.byref(ev_ovh))
+        probe("J'u pass + overhead")
     region_s_local = list(region_s)
     own_srt = sorted(region_s_local)
     own_rate = a.steps / own_srt[len(own_srt) // 2]
@@ -294,15 +311,16 @@ def main():
     inner_total /= reps                                  # per region
     real_total /= reps                                   # working LM iterations of all ranks per region (N = 1: exactly K)
 
-    # generic J*v (y <- J x + y) timed back-to-back with HIP events, for reference
-    xv = lsq.DeviceVector(ctx, n, np.random.default_rng(0).standard_normal(n))
-    yv = lsq.DeviceVector(ctx, m, np.zeros(m))
-    ms = C.c_float(0)
-    lsq._lib.check(L.lsq_bench_mul(pr.J, 0, 50, xv.ptr, yv.ptr, 1.0, C.byref(ms)))
-    ms_t = C.c_float(0)
-    lsq._lib.check(L.lsq_bench_mul(pr.J, 1, 50, yv.ptr, xv.ptr, 1.0, C.byref(ms_t)))
+    if a.full:
+        # generic J*v (y <- J x + y) timed back-to-back with HIP events, for reference
+        xv = lsq.DeviceVector(ctx, n, np.random.default_rng(0).standard_normal(n))
+        yv = lsq.DeviceVector(ctx, m, np.zeros(m))
+        ms = C.c_float(0)
+        lsq._lib.check(L.lsq_bench_mul(pr.J, 0, 50, xv.ptr, yv.ptr, 1.0, C.byref(ms)))
+        ms_t = C.c_float(0)
+        lsq._lib.check(L.lsq_bench_mul(pr.J, 1, 50, yv.ptr, xv.ptr, 1.0, C.byref(ms_t)))
 
-    probe("lsq_bench_mul")
+        probe("lsq_bench_mul")
 
     def leave_group():
         if dist is not None:
@@ -317,39 +335,41 @@ def main():
         leave_group()
         return
 
-    bytes_jv = 12 * nnz + 4 * (m + 1) + 8 * n + 16 * m      # SURVEY 8d (CSR mirror, beta != 0)
-    bytes_k1 = bytes_jv + 24 * n                            # + fused damping rows (t, dg, ux rw)
-    bytes_jtu = 12 * nnz + 4 * (n + 1) + 8 * m + 16 * n
-    # the two events are the launch's own start/stop events (hipExtLaunchKernelGGL): they carry the
-    # dispatch's begin/end timestamps, i.e. the duration rocprofv3 reports -- no marker overhead
-    k1_raw_ms = avg[0] if cnt[0] > 0 else float("nan")
-    k1_ms = k1_raw_ms
-    achieved = bytes_k1 / (k1_ms * 1e-3) / 1e9 if cnt[0] > 0 else None
     three = not os.environ.get("LSQ_LSMR_FOUR_LAUNCHES") and n <= 12160
-    roof = {"bound": "hbm", "kernel": ("k_lsmr_fused (LSMR J*v: u <- (J w)/alpha - cu*u, + sum u^2; the n-vector updates and the stop test of "
-                                        "the previous iteration ride in 3 extra workgroups)" if three else
-                                        "k_sell_rows<EpiU> (LSMR J*v: u <- J t - cu*u, + sum u^2)"),
-            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": None,
-            "algorithmic_bytes_per_launch": bytes_k1, "avg_launch_ms": k1_ms, "launches_timed": int(cnt[0]),
-            "timing": "HIP start/stop events of the launch itself (hipExtLaunchKernelGGL) on the library stream",
-            "empty_event_pair_ms": ev_ovh.value,
-            "jtu_kernel_avg_ms": avg[1],
-            "jtu_GBps": (bytes_jtu + 16 * n) / (avg[1] * 1e-3) / 1e9 if cnt[1] else None,
-            "generic_jv_ms": ms.value, "generic_jv_GBps": bytes_jv / (ms.value * 1e-3) / 1e9,
-            "generic_jtu_ms": ms_t.value, "generic_jtu_GBps": bytes_jtu / (ms_t.value * 1e-3) / 1e9}
+    roof = None
+    if a.full:
+        bytes_jv = 12 * nnz + 4 * (m + 1) + 8 * n + 16 * m      # SURVEY 8d (CSR mirror, beta != 0)
+        bytes_k1 = bytes_jv + 24 * n                            # + fused damping rows (t, dg, ux rw)
+        bytes_jtu = 12 * nnz + 4 * (n + 1) + 8 * m + 16 * n
+        # the two events are the launch's own start/stop events (hipExtLaunchKernelGGL): they carry the
+        # dispatch's begin/end timestamps, i.e. the duration rocprofv3 reports -- no marker overhead
+        k1_raw_ms = avg[0] if cnt[0] > 0 else float("nan")
+        k1_ms = k1_raw_ms
+        achieved = bytes_k1 / (k1_ms * 1e-3) / 1e9 if cnt[0] > 0 else None
+        roof = {"bound": "hbm", "kernel": ("k_lsmr_fused (LSMR J*v: u <- (J w)/alpha - cu*u, + sum u^2; the n-vector updates and the stop test of "
+                                            "the previous iteration ride in 3 extra workgroups)" if three else
+                                            "k_sell_rows<EpiU> (LSMR J*v: u <- J t - cu*u, + sum u^2)"),
+                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": None,
+                "algorithmic_bytes_per_launch": bytes_k1, "avg_launch_ms": k1_ms, "launches_timed": int(cnt[0]),
+                "timing": "HIP start/stop events of the launch itself (hipExtLaunchKernelGGL) on the library stream",
+                "empty_event_pair_ms": ev_ovh.value,
+                "jtu_kernel_avg_ms": avg[1],
+                "jtu_GBps": (bytes_jtu + 16 * n) / (avg[1] * 1e-3) / 1e9 if cnt[1] else None,
+                "generic_jv_ms": ms.value, "generic_jv_GBps": bytes_jv / (ms.value * 1e-3) / 1e9,
+                "generic_jtu_ms": ms_t.value, "generic_jtu_GBps": bytes_jtu / (ms_t.value * 1e-3) / 1e9}
 
-    # HBM traffic of that kernel comes from rocprofv3 PMC passes (it cannot be read inside this
-    # process): the committed measurement for exactly this workload, newest round first
-    for rnd in sorted((d for d in os.listdir(os.path.join(ROOT, "profiles")) if d.startswith("r")), reverse=True):
-        try:
-            tr = json.load(open(os.path.join(ROOT, "profiles", rnd, "pmc_traffic.json")))
-            if tr["config"] == {"m": m, "n": n, "nnz": nnz}:
-                roof["traffic"] = tr["hbm_bytes_per_launch"]
-                roof["traffic_source"] = tr["source"]
-                break
-        except Exception:
-            pass
+        # HBM traffic of that kernel comes from rocprofv3 PMC passes (it cannot be read inside this
+        # process): the committed measurement for exactly this workload, newest round first
+        for rnd in sorted((d for d in os.listdir(os.path.join(ROOT, "profiles")) if d.startswith("r")), reverse=True):
+            try:
+                tr = json.load(open(os.path.join(ROOT, "profiles", rnd, "pmc_traffic.json")))
+                if tr["config"] == {"m": m, "n": n, "nnz": nnz}:
+                    roof["traffic"] = tr["hbm_bytes_per_launch"]
+                    roof["traffic_source"] = tr["source"]
+                    break
+            except Exception:
+                pass
 
     # (the headline measurement is complete at this point: a failure in the reported-alongside legs must not lose it)
     # Order: the device-only secondary legs FIRST.  The OpenMP legs after them (oracle/lsq_oracle_omp.c under
@@ -358,20 +378,20 @@ def main():
     # (either one alone: 8.0; putting this thread's affinity mask back did not cure it).
     skip = set(filter(None, os.environ.get("LSQ_BENCH_SKIP", "").split(",")))     # diagnostics: legs to leave out (generic, dense, wide)
     dense = None
-    if not a.no_cpu and world == 1 and not a.no_dense and "dense" not in skip:
+    if a.full and not a.no_cpu and world == 1 and not a.no_dense and "dense" not in skip:
         try:
             dense = dense_secondary(ctx, lsq, probe)
         except Exception as e:   # noqa: BLE001
             dense = {"error": repr(e)}
 
     wide = None
-    if not a.no_cpu and world == 1 and "wide" not in skip:
+    if a.full and not a.no_cpu and world == 1 and "wide" not in skip:
         try:
             wide = sparse_secondary(ctx, lsq)
         except Exception as e:   # noqa: BLE001
             wide = {"error": repr(e)}
     cpu = parity = None
-    if not a.no_cpu and a.cpu_steps > 0 and world == 1:   # reported at N = 1 only
+    if a.full and not a.no_cpu and a.cpu_steps > 0 and world == 1:   # reported at N = 1 only
         try:
             # the solve the timed region repeats, once more with its trace kept: the CPU leg's first solve is the same
             # problem on the same schedule, so the two trajectories are compared instead of thrown away; and the
@@ -386,7 +406,7 @@ def main():
     # the schedule of rounds 1-5 beside the headline: solves of --iters-per-solve (8) iterations with zero tolerances, i.e. two
     # cheap one-inner-iteration steps past convergence per solve (they flatter the rate: never `value`)
     fixed_sched = None
-    if world == 1:
+    if a.full and world == 1:
         try:
             run(a.iters_per_solve, fixed=a.iters_per_solve)
             ts = []
@@ -403,7 +423,7 @@ def main():
         except Exception as e:   # noqa: BLE001
             fixed_sched = {"error": repr(e)}
     generic = None
-    if not a.no_cpu and world == 1 and "generic" not in skip:
+    if a.full and not a.no_cpu and world == 1 and "generic" not in skip:
         try:
             generic = generic_g(a, ctx, lsq, inputs, pr.b)
         except Exception as e:   # noqa: BLE001
@@ -435,12 +455,13 @@ def main():
             "wide_lm_lsmr_outer_ms": g(wide, "lm_lsmr_outer_iteration_ms"),
             "tail_guesses": tail_timed[0], "tail_wrong": tail_timed[1],
             "tail_wrong_frac": (tail_timed[1] / tail_timed[0]) if tail_timed[0] else None}
-    roof["jtu_frac"] = (roof["jtu_GBps"] / HBM_PEAK_GBS) if roof.get("jtu_GBps") else None
-    # the PHYSICAL rate of the dominant kernel beside the algorithmic one: PMC bytes per launch / the launch's duration
-    roof["physical_GBps"] = (roof["traffic"] / (k1_ms * 1e-3) / 1e9) if (roof.get("traffic") and cnt[0] > 0) else None
-    roof["physical_frac"] = (roof["physical_GBps"] / HBM_PEAK_GBS) if roof["physical_GBps"] else None
-    for k in ("c2_ldiv_ms", "c2_frac", "c3_ldiv_ms", "c3_frac", "wide_jv_frac", "wide_jtu_frac"):
-        roof[k] = flat[k]
+    if roof is not None:
+        roof["jtu_frac"] = (roof["jtu_GBps"] / HBM_PEAK_GBS) if roof.get("jtu_GBps") else None
+        # the PHYSICAL rate of the dominant kernel beside the algorithmic one: PMC bytes per launch / the launch's duration
+        roof["physical_GBps"] = (roof["traffic"] / (k1_ms * 1e-3) / 1e9) if (roof.get("traffic") and cnt[0] > 0) else None
+        roof["physical_frac"] = (roof["physical_GBps"] / HBM_PEAK_GBS) if roof["physical_GBps"] else None
+        for k in ("c2_ldiv_ms", "c2_frac", "c3_ldiv_ms", "c3_frac", "wide_jv_frac", "wide_jtu_frac"):
+            roof[k] = flat[k]
     config = {"workload": "C4: sparse CSC %dx%d, nnz=%d (%.3g%%), LevenbergMarquardt(LSMR()), tanh model, "
                           "1 problem per GPU" % (m, n, nnz, 100.0 * nnz / (m * n)),
               "schedule": "reference: solves from x0 = 0 with the default tolerances (1e-8), each stopping at convergence "
@@ -506,6 +527,29 @@ def main():
     os.write(real_stdout, (json.dumps(out) + "\n").encode())   # fd 1 stays on stderr: RCCL prints its banner at exit
     if out.get("invalid"):
         raise SystemExit(3)
+
+
+DUMP_LIMIT_BYTES = 48 << 20      # (the whole dump stays under 64 MB, .npy headers included)
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy in float64.  An array larger than its share of DUMP_LIMIT_BYTES is written
+    as a fixed sample instead (seed 0, sorted positions): d/<name>_sample.npy and the positions as d/<name>_sample_index.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64).ravel() for k, v in arrays.items()}
+    left = DUMP_LIMIT_BYTES
+    for i, (name, v) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].nbytes)):
+        share = left // (len(arrays) - i)
+        if v.nbytes <= share:
+            np.save(os.path.join(d, name + ".npy"), v)
+            left -= v.nbytes
+        else:
+            idx = np.sort(np.random.default_rng(0).choice(v.size, share // 16, replace=False))
+            np.save(os.path.join(d, name + "_sample.npy"), v[idx])
+            np.save(os.path.join(d, name + "_sample_index.npy"), idx.astype(np.float64))
+            left -= 16 * idx.size
+    print("bench: outputs of the last timed solve written to %s" % d, file=sys.stderr)
 
 
 def lsmr_iteration_text(three):

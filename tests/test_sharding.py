@@ -630,3 +630,24 @@ def test_bench_forced_exchange_runs_on_rccl():
     assert j["n_gpus"] == 1 and j["config"]["exchange_backend"] == "rccl-c" and j["config"]["rccl_ranks"] == 1
     assert j["config"]["exchange"]["collectives"] > 0
     assert j["value"] > 0 and j["repeats"] == 3 and j["region_ms"]["min"] <= j["region_ms"]["median"] <= j["region_ms"]["max"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_k_steps_and_dumps_outputs(tmp_path):
+    """A plain `bench.py` run: ONE timed region of exactly --steps steps, the headline only (the companion legs are --full's),
+    and --dump-outputs writes what the last timed solve returned."""
+    import numpy as np
+    m, n = 20000, 200
+    j = _bench_line(["--steps", "10", "--warmup", "2", "--m", str(m), "--n", str(n), "--per-col", "100",
+                     "--dump-outputs", str(tmp_path)])
+    assert j["metric"] == "lm_lsmr_outer_iterations_per_sec" and j["unit"] == "LM outer iterations/s" and j["dtype"] == "f64"
+    assert j["higher_is_better"] is True and j["steps"] == 10 and j["repeats"] == 1
+    assert j["value"] > 0 and j["ms_per_step"] == pytest.approx(1e3 / j["value"], rel=1e-9)
+    assert j["roofline"] is None and j["cpu_baseline"] is None and j["parity_vs_cpu"] is None
+    x, f = np.load(tmp_path / "minimizer.npy"), np.load(tmp_path / "residual.npy")
+    ssr, counts = np.load(tmp_path / "ssr.npy"), np.load(tmp_path / "counts.npy")
+    assert x.dtype == f.dtype == ssr.dtype == counts.dtype == np.float64
+    assert x.shape == (n,) and f.shape == (m,) and counts.shape == (6,)
+    assert np.all(np.isfinite(x)) and np.all(np.isfinite(f)) and 0 < counts[0] <= 10
+    assert ssr[0] == pytest.approx(j["config"]["final_ssr"], rel=1e-15)
+    assert float(np.sum(f * f)) == pytest.approx(ssr[0], rel=1e-9)

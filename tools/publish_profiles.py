@@ -18,7 +18,7 @@ k1 = [l for l in table.splitlines() if "k_lsmr_fused" in l and "grid=262144" in 
 K1NAME = "k_lsmr_fused" if any("k_lsmr_fused" in l for l in k1) else "k_sell_rows<EpiU>"
 k1_work = float(k1[0].split("|")[5]) if k1 else float("nan")
 with open(os.path.join(dst, "kernel_summary.md"), "w") as fh:
-    fh.write("# rocprofv3 --kernel-trace of `python bench.py --no-cpu`, per kernel\n\n"
+    fh.write("# rocprofv3 --kernel-trace of `python bench.py --full --no-cpu`, per kernel\n\n"
              "`--stats` (bench_kernel_stats.csv) averages the early-exit launches of finished LSMR solves together\n"
              "with the working launches; this table separates them.  The LSMR J*v kernel is `" + K1NAME + "`:\n"
              "its working-launch average here (%.2f us) is what `roofline.avg_launch_ms` measures with the launch's\n"
@@ -48,7 +48,7 @@ cfg = bench["config"]
 with open(os.path.join(dst, "pmc_traffic.md"), "w") as fh:
     fh.write(pm)
     fh.write("\nCollected with two separate passes of `rocprofv3 --kernel-trace --pmc FETCH_SIZE` / `--pmc WRITE_SIZE`\n"
-             "over `python bench.py --no-cpu --steps 16 --warmup 8` (working launches only; counters in KiB).\n"
+             "over `python bench.py --full --no-cpu --steps 16 --warmup 8` (working launches only; counters in KiB).\n"
              "HBM bytes = (2*FETCH_SIZE + WRITE_SIZE) * 1024: the gfx950 correction of MI355X_MICROARCH.md (FETCH_SIZE\n"
              "reports half of the bytes of wide coalesced reads).  In-run calibration on a kernel with known traffic:\n")
     if cal:
