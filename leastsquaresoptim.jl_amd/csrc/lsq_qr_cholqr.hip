@@ -17,10 +17,11 @@
 //   S = diag(+-1) from the modified LU of Q_top (S_j = -sign of the running diagonal, pivots >= 1 in magnitude),
 //   V = Q - [S; 0],   B = Q_top - S = L U,   Qfull = I - V T V',  T' = -inv(B) S,  Qfull' P = [S R2 R1; 0]
 //
-// so the existing block update applies unchanged:  W = V'[A2 | b] (k_qr1_vtb),  W2 = T'W = inv(B)(A2_top - S Q'[A2|b])
-// (k_cqr_tw, one 64 x 64 x N MFMA product),  A2 -= V W2 (k_qr1_update).  The 64-step LU runs in ONE workgroup on a side
-// stream (k_cqr_top: it needs the top 64 rows only, so it starts as soon as G2 is known and runs beside pass 2 and the
-// V'A2 product), off the critical path for all but the narrowest trailing matrices.  Small-matrix work: lsq_small64.h.
+// so the existing block update applies:  W = V'[A2 | b] (k_qr1_vtb),  W2 = T'W = inv(B)(A2_top - S Q'[A2|b]),  A2 -= V W2
+// (k_qr1_update).  Pass 2 over the panel is never run: Q = Q1 inv(R2) is not formed, the trailing kernels take Q1 and the
+// small factor inv(R2) is folded into the 64 x N matrices (k_cqr_tw_q1, the Q1 form below).  R2 and the 64-step LU run in ONE
+// workgroup on a side stream (k_cqr_top: it needs G2 and the top 64 rows only, so it runs beside the V'A2 product), off the
+// critical path for all but the narrowest trailing matrices.  Small-matrix work: lsq_small64.h.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -35,12 +36,11 @@
 // (Look-ahead -- panel k+1's passes on a high-priority stream beside the update of panel k -- was built on top of this in
 //  round 3 and measured: the passes do start beside the LDS-staged update, but both stretch; 8.0 ms against 7.55 at C3.
 //  Round 5 built it again on the LDS-free update, lsq_qr_stage1.hip: qr2_factor_core, and with ONE factor workgroup per pass,
-//  k_cqr_factor below: 7.20 -> 7.06 ms at C3, taken while >= 1024 other columns remain.)
+//  k_cqr_factor below; since round 6 it is taken for panels taller than the device's CUs' worth of slabs.)
 constexpr int CQ_LDS_DOUBLES = 2 * S64_MAT + S64_TMP;
 static_assert(S64_MAT + S64_TMP >= 64 * CQ_QST, "slab image over R + scratch");
 constexpr size_t CQ_LDS = (size_t)CQ_LDS_DOUBLES * sizeof(double);
 constexpr size_t CQ_LDS_LU = (size_t)(4 * S64_MAT + S64_TMP) * sizeof(double);
-constexpr size_t CQ_LDS_TW = (size_t)(2 * S64_MAT) * sizeof(double);
 #ifdef CQ_TIMING   // phase time stamps of workgroup 0 (tools/micro/cqr_bench.hip only)
 __device__ unsigned long long cq_tbuf[64];
 #define CQ_T(k) do { if (blockIdx.x == 0 && threadIdx.x == 0) cq_tbuf[k] = wall_clock64(); } while (0)
@@ -74,10 +74,11 @@ __device__ __forceinline__ void cq_load64(double *__restrict__ dst, const double
 // inverse; the caller substitutes (cq_rows_trsm).
 template <int PASS, bool NOINV = false>
 __device__ __forceinline__ void cq_factor(const double *__restrict__ G, double *__restrict__ M1, double *__restrict__ M2,
-                                          double *__restrict__ T, int *s_fail, double *s_red, int *bad, int tid, int ngroups = 0) {
+                                          double *__restrict__ T, int *s_fail, double *s_red, int *bad, int tid) {
     const int lane = tid & 63, wv = tid >> 6;
     double g[16];
-    cq_gram_entries(G, ngroups, g, tid);                          // entry e = tid + 256 q: row e >> 6, column e & 63
+#pragma unroll
+    for (int q = 0; q < 16; ++q) g[q] = G[tid + 256 * q];        // entry e = tid + 256 q: row e >> 6, column e & 63
     *bad = 0;
     bool series = false, first_order = false;
     if (PASS == 2) {
@@ -213,18 +214,15 @@ __device__ __forceinline__ void cq_rows_times_inv(const double *__restrict__ P, 
     cq_rows_mma(a, M2, acc, lane);
 }
 
-// PASS 0: Gram partials of the raw panel.   PASS 1: R1 = chol(G), Q1 = P inv(R1) in place, Gram partials of Q1.
-// PASS 2: R2 from G2 = Q1'Q1, Q = Q1 inv(R2) -> Vb.      P = A(c0 + [0, rows), c0 + [0, 64)), column-major, ld lda.
-// PRE: inv(R) was computed once by k_cqr_factor (G points at it) instead of by every workgroup -- the look-ahead panel, whose
+// PASS 0: Gram partials of the raw panel.   PASS 1: R1 = chol(G), Q1 = P inv(R1) -> Vb (and Vs), Gram partials of Q1.
+// P = A(c0 + [0, rows), c0 + [0, 64)), column-major, ld lda.
+// PRE: inv(R1) was computed once by k_cqr_factor (G points at it) instead of by every workgroup -- the look-ahead panel, whose
 // passes share the CUs with the trailing update: 256 redundant 64 x 64 factorisations are 18 us of every CU's ALU and LDS time.
 template <int PASS, bool PRE = false>
 __global__ void __launch_bounds__(256)
 k_cqr_pass(double *__restrict__ A, int lda, int c0, int rows, const double *__restrict__ G, double *__restrict__ Gp,
-           double *__restrict__ R1g, double *__restrict__ Vb, int ldv, int *__restrict__ err, int q1vb = 0 /* PASS 1: Q1 -> Vb
-           instead of in place (the Q1 form of the block reflector, round 6: no pass 2) */,
-           int ngroups_in = 0 /* > 0: G holds that many group sums (cq_group_reduce), added here */,
-           double *Gq = nullptr /* non-null: this launch's own partials are summed per group into Gq */, unsigned *gcnt = nullptr,
-           double *__restrict__ Vs = nullptr /* PASS 1, q1vb: Q1 also in V'B's fragment order (lsq_cqr_vs_index) */) {
+           double *__restrict__ R1g, double *__restrict__ Vb, int ldv, int *__restrict__ err,
+           double *__restrict__ Vs = nullptr /* PASS 1: Q1 also in V'B's fragment order (lsq_cqr_vs_index) */) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     double *M2 = sm, *M1 = sm + S64_MAT, *T = sm + 2 * S64_MAT, *Qs = M1;   // (Qs aliases R and the scratch: used after them)
     __shared__ int s_fail;
@@ -245,11 +243,7 @@ k_cqr_pass(double *__restrict__ A, int lda, int c0, int rows, const double *__re
         for (int q = 0; q < 16; ++q) Qs[(cq + 4 * q) * CQ_QST + row] = rin ? t[q] : 0.0;
         __syncthreads();
         CQ_T(1);
-        if (Gq) {
-            cq_slab_gram<true>(Qs, Gp + (size_t)slab * 4096, tid);
-            cq_group_reduce(Gp, Gq, gcnt, slab, (int)gridDim.x, tid);
-        } else
-            cq_slab_gram(Qs, Gp + (size_t)slab * 4096, tid);
+        cq_slab_gram(Qs, Gp + (size_t)slab * 4096, tid);
         CQ_T(2);
         return;
     }
@@ -259,13 +253,13 @@ k_cqr_pass(double *__restrict__ A, int lda, int c0, int rows, const double *__re
         cq_load64(M2, G, tid);                                    // inv(R), row-major 64 x 64
     } else {
         int bad;
-        cq_factor<PASS, PASS == 1>(G, M1, M2, T, &s_fail, s_red, &bad, tid, ngroups_in);     // every workgroup, identically
+        cq_factor<PASS, PASS == 1>(G, M1, M2, T, &s_fail, s_red, &bad, tid);     // every workgroup, identically
         if (bad && slab == 0 && tid == 0) atomicOr(err, CQ_FAIL);
         CQ_T(PASS * 16 + 2);
         if (PASS == 1 && slab == 0)
             for (int e = tid; e < 4096; e += 256) R1g[e] = M1[(e >> 6) * S64_LS + (e & 63)];
     }
-    __syncthreads();                                              // (PRE / pass 2: R is dead from here on: its LDS becomes the slab image)
+    __syncthreads();                                              // (PRE: R is dead from here on: its LDS becomes the slab image)
     // ---- slab product  Qslab = Pslab * inv(R) ------------------------------------------------------------------
     CQ_T(PASS * 16 + 3);
     if (PASS == 1 && !PRE) {
@@ -289,17 +283,15 @@ k_cqr_pass(double *__restrict__ A, int lda, int c0, int rows, const double *__re
     }
     __syncthreads();
     CQ_T(PASS * 16 + 4);
-    const bool inplace = PASS == 1 && !q1vb;
-    double *dst = inplace ? P : Vb + r0;
-    const size_t ldd = inplace ? (size_t)lda : (size_t)ldv;
     {
+        double *dst = Vb + r0;
         const int row = tid & (CQ_RS - 1), cq = tid >> 6;
         if (row < nr) {
 #pragma unroll
-            for (int q = 0; q < 16; ++q) dst[(cq + 4 * q) * ldd + row] = Qs[(cq + 4 * q) * CQ_QST + row];
+            for (int q = 0; q < 16; ++q) dst[(cq + 4 * q) * (size_t)ldv + row] = Qs[(cq + 4 * q) * CQ_QST + row];
         }
     }
-    if (PASS == 1 && Vs && q1vb) {
+    if (PASS == 1 && Vs) {
         // the slab's full 16-row chunks once more, in the order in which k_qr1_vtb_w's lanes consume them (1 KB contiguous per
         // load instruction there): block = (chunk, 16-column tile it, half h), lane = ij + 16 kq, two doubles per lane
 #pragma unroll
@@ -316,13 +308,7 @@ k_cqr_pass(double *__restrict__ A, int lda, int c0, int rows, const double *__re
         }
     }
     CQ_T(PASS * 16 + 5);
-    if (PASS == 1) {
-        if (Gq) {
-            cq_slab_gram<true>(Qs, Gp + (size_t)slab * 4096, tid);
-            cq_group_reduce(Gp, Gq, gcnt, slab, (int)gridDim.x, tid);
-        } else
-            cq_slab_gram(Qs, Gp + (size_t)slab * 4096, tid);
-    }
+    if (PASS == 1) cq_slab_gram(Qs, Gp + (size_t)slab * 4096, tid);
     CQ_T(PASS * 16 + 6);
 }
 
@@ -378,20 +364,17 @@ __global__ void __launch_bounds__(256) k_cqr_reduce(const double *__restrict__ G
     }
 }
 
-// ONE workgroup, on the side stream, beside pass 2 and the caller's V'[A2 | b] product: everything that hangs on the TOP
-// 64 rows only.  It repeats pass 2's factor and forms Q_top = Q1_top inv(R2) itself (so it needs nothing from pass 2),
-// then: modified LU of B = Q_top - S (S on the fly), inv(B) = inv(U) inv(L) and S -> global;
-// R = R2 R1 and the panel's part of the factor, S R, -> SRg (64 x 64, [col][row]).  It does NOT store into A: pass 2 runs
-// beside it on the main stream and its slab 0 reads Q1's top rows from exactly the elements S R belongs in (a write
-// after read with nothing ordering it -- the round-3 defect: a host stall between the two launches let the store win and
-// slab 0 built V's top rows from S R).  k_cqr_tw, behind both kernels, moves SRg into A's triangle.
-// Q1 form (round 6, R2inv != null): there is no pass 2 at all -- the block reflector is applied with Q1 and the small factor
-// inv(R2) is folded into the 64 x N matrices (k_cqr_tw_q1), so this kernel also hands out inv(R2), reads Q1's top rows from
-// where pass 1 left them (Vb: Q1top / ldq) and raises the breakdown flag that pass 2 used to raise.
+// ONE workgroup, on the side stream, beside the caller's V'[A2 | b] product: everything that hangs on the TOP 64 rows only.
+// There is no pass 2 over the panel: the block reflector is applied with Q1 and the small factor inv(R2) is folded into the
+// 64 x N matrices (k_cqr_tw_q1).  This kernel forms R2 (and hands out inv(R2)) from G2 = Q1'Q1, raises the breakdown flag, and
+// forms Q_top = Q1_top inv(R2) from Q1's top rows (Vb: Q1top / ldq); then: the kernel of the block reflector, inv(B) with
+// B = Q_top - S, and S -> global; R = R2 R1 and the panel's part of the factor, S R, -> SRg (64 x 64, [col][row]).  It does
+// NOT store into A (round 3's defect, tools/repro/qr_race.py, was such a store racing a reader of the panel on the main
+// stream); k_cqr_tw_q1, behind this kernel, moves SRg into A's triangle.
 __global__ void __launch_bounds__(256)
 k_cqr_top(const double *__restrict__ G2, const double *__restrict__ R1g, const double *__restrict__ Q1top, int ldq,
           double *__restrict__ Binv, double *__restrict__ Sg, double *__restrict__ SRg, int *__restrict__ err,
-          double *__restrict__ R2inv, int lu_only, int ngroups) {
+          double *__restrict__ R2inv, int lu_only) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     double *B0 = sm, *B1 = sm + S64_MAT, *B2 = sm + 2 * S64_MAT, *B3 = sm + 3 * S64_MAT, *T = sm + 4 * S64_MAT;
     __shared__ double sS[64], sR[64], s_red[4];
@@ -401,16 +384,14 @@ k_cqr_top(const double *__restrict__ G2, const double *__restrict__ R1g, const d
     // (this workgroup is a chain of latencies on every panel's path: what comes from memory -- Q1's top rows, R1 -- is requested
     //  before the factor, together with G2)
     double qtop[16], r1v[16];
-    cq_rows_fetch(Q1top, (size_t)ldq, 64, qtop, lane, wv);         // Q1's top rows (pass 1: in place in A, or in Vb)
+    cq_rows_fetch(Q1top, (size_t)ldq, 64, qtop, lane, wv);         // Q1's top rows (pass 1 left them in Vb)
 #pragma unroll
     for (int q = 0; q < 16; ++q) r1v[q] = R1g[tid + 256 * q];
     int bad;
-    cq_factor<2>(G2, B0, B1, T, &s_fail, s_red, &bad, tid, ngroups);   // B0 = R2, B1 = inv(R2)  (old form: the flag is raised by pass 2)
-    if (R2inv) {
-        if (bad && tid == 0) atomicOr(err, CQ_FAIL);
+    cq_factor<2>(G2, B0, B1, T, &s_fail, s_red, &bad, tid);        // B0 = R2, B1 = inv(R2)
+    if (bad && tid == 0) atomicOr(err, CQ_FAIL);
 #pragma unroll
-        for (int q = 0; q < 16; ++q) { const int e = tid + 256 * q; R2inv[e] = B1[(e >> 6) * S64_LS + (e & 63)]; }
-    }
+    for (int q = 0; q < 16; ++q) { const int e = tid + 256 * q; R2inv[e] = B1[(e >> 6) * S64_LS + (e & 63)]; }
 #pragma unroll
     for (int q = 0; q < 16; ++q) { const int e = tid + 256 * q; B2[(e >> 6) * S64_LS + (e & 63)] = r1v[q]; }
     __syncthreads();
@@ -507,7 +488,7 @@ k_cqr_top(const double *__restrict__ G2, const double *__restrict__ R1g, const d
     double *M = B2, *Li = B0;
     s64_lu_modified(M, Li, sS, sR, tid);
     CQ_T(50);
-    // the panel's part of the factor, S R (upper triangle; zeros below), for k_cqr_tw to put into A
+    // the panel's part of the factor, S R (upper triangle; zeros below), for k_cqr_tw_q1 to put into A
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
         const int e = tid + 256 * q, col = e >> 6, row = e & 63;
@@ -538,67 +519,6 @@ k_cqr_top(const double *__restrict__ G2, const double *__restrict__ R1g, const d
     CQ_T(52);
 }
 
-// W2(:, 64 columns of the workgroup) = inv(B) (A2_top - S W_Q)   [W = V'[V | A2 | b] with V = Q, from k_qr1_vtb + wreduce]
-// B-matrix column cb >= 64 is A(:, cend + cb - 64) or the right-hand side (last column); rows from c0.
-__global__ void __launch_bounds__(256)
-k_cqr_tw(const double *__restrict__ W, int ncolsB, const double *__restrict__ Binv, const double *__restrict__ Sg,
-         const double *__restrict__ SRg, double *A /* read: trailing columns' top rows; written: the panel's triangle */, int lda,
-         int c0, int cend, int n, const double *__restrict__ rhs, double *__restrict__ Vb, int ldv, double *__restrict__ W2) {
-    extern __shared__ __attribute__((aligned(16))) double sm[];
-    double *sBi = sm;                      // inv(B), row-major
-    double *sRh = sm + S64_MAT;            // RHS[k][j]
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int ncols = ncolsB - 64, j0 = blockIdx.x * 64;
-    if ((int)blockIdx.x == (int)gridDim.x - 1) {
-        // ONE EXTRA workgroup, beside the ones that form W2: V = Q - [S; 0] for the update, and the panel's part of R -> A.
-        // (This launch is ordered behind pass 2 -- the last reader of Q1's top rows -- by the stream and behind k_cqr_top by
-        //  ev_lu; nothing in this kernel reads the panel's columns of A.  In workgroup 0, as first written in round 4, the
-        //  copy put a memory round trip in front of that workgroup's product: 11.2 instead of 7.7 us per launch.)
-        if (tid < 64) Vb[(size_t)tid * ldv + tid] -= Sg[tid];
-        double t[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) t[q] = SRg[tid + 256 * q];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int e = tid + 256 * q, col = e >> 6, row = e & 63;
-            if (row <= col) A[(size_t)(c0 + col) * lda + c0 + row] = t[q];
-        }
-        return;
-    }
-    cq_load64(sBi, Binv, tid);
-    {
-        double top[16], wq[16];
-        const double sk = Sg[tid & 63];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int e = tid + 256 * q, j = e >> 6, k = e & 63, col = min(j0 + j, ncols - 1), a = cend + col;
-            top[q] = a < n ? A[(size_t)a * lda + c0 + k] : rhs[c0 + k];
-            wq[q] = W[(size_t)(64 + col) * 64 + k];
-        }
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int e = tid + 256 * q, j = e >> 6, k = e & 63;
-            sRh[k * S64_LS + j] = j0 + j < ncols ? top[q] - sk * wq[q] : 0.0;
-        }
-    }
-    __syncthreads();
-    const int ij = lane & 15, kq = lane >> 4;
-    for (int q = wv; q < 16; q += 4) {
-        const int ti = q >> 2, tj = q & 3;
-        s64_v4d acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const int k = s * 4 + kq;
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(sBi[(16 * ti + ij) * S64_LS + k], sRh[k * S64_LS + 16 * tj + ij], acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = 16 * ti + kq + 4 * r, col = j0 + 16 * tj + ij;
-            if (col < ncols) W2[(size_t)col * 64 + row] = acc[r];
-        }
-    }
-}
-
 // Q1 FORM of the block reflector (round 6).  With Q = Q1 inv(R2), V = Q - [S; 0]:
 //      V'[A2 | b] = inv(R2)' (Q1'[A2 | b]) - S A2_top          A2 - V W2 = A2 - Q1 (inv(R2) W2) + [S W2; 0]
 // so pass 2 over the panel (Q = Q1 inv(R2) -> Vb: a launch of 13 us on the critical path of every panel, plus the Gram reduce
@@ -607,7 +527,7 @@ k_cqr_tw(const double *__restrict__ W, int ncolsB, const double *__restrict__ Bi
 //      WQ = inv(R2)' W;   W2 = inv(B)(A2_top - S WQ);   A2_top += S W2  (written back: every workgroup owns its 64 columns);
 //      W3 = inv(R2) W2 -> the update kernel's operand (it then subtracts Q1 W3 from ALL rows of A2, the top ones included).
 // R2inv, Binv, S, SR: k_cqr_top on the side stream (ev_lu).  The extra workgroup puts the panel's part of R into A.
-// SIXTEEN columns per workgroup (the first form took 64, like k_cqr_tw: three dependent 64^3 products by one CU -- 144 MFMAs per
+// SIXTEEN columns per workgroup (the first form took 64: three dependent 64^3 products by one CU -- 144 MFMAs per
 // wavefront at one per ~100 clocks -- made the launch 15 us on every panel's path; with 16 columns a wavefront owns ONE 16 x 16 tile
 // of each product, at most 16 MFMAs, and four times as many CUs share the work).
 constexpr int TQ_NC = 16;                  // columns of [A2 | b] per workgroup
@@ -718,14 +638,8 @@ int lsq_cqr_alloc(lsq_ctx *c, CqrWork *w, int M) {
     LSQ_HIP(hipMalloc(&w->R1, 4096 * sizeof(double)));
     LSQ_HIP(hipMalloc(&w->G2, 4096 * sizeof(double)));
     LSQ_HIP(hipMalloc(&w->Binv, 4096 * sizeof(double)));
-    LSQ_HIP(hipMalloc(&w->Minv, 2 * 4096 * sizeof(double)));
+    LSQ_HIP(hipMalloc(&w->Minv, 4096 * sizeof(double)));
     LSQ_HIP(hipMalloc(&w->R2inv, 4096 * sizeof(double)));
-    LSQ_HIP(hipMalloc(&w->Gq1, (size_t)CQ_HIER_MAX_GROUPS * 4096 * sizeof(double)));
-    LSQ_HIP(hipMalloc(&w->Gq2, (size_t)CQ_HIER_MAX_GROUPS * 4096 * sizeof(double)));
-    LSQ_HIP(hipMalloc(&w->gcnt, CQ_HIER_MAX_GROUPS * sizeof(unsigned)));
-    LSQ_ZERO(w->Gq1, 0, (size_t)CQ_HIER_MAX_GROUPS * 4096 * sizeof(double));     // (the strictly lower tiles are never written)
-    LSQ_ZERO(w->Gq2, 0, (size_t)CQ_HIER_MAX_GROUPS * 4096 * sizeof(double));
-    LSQ_ZERO(w->gcnt, 0, CQ_HIER_MAX_GROUPS * sizeof(unsigned));
     LSQ_HIP(hipMalloc(&w->S, 64 * sizeof(double)));
     LSQ_HIP(hipMalloc(&w->SR, 4096 * sizeof(double)));
     {   // highest priority: k_cqr_top's single workgroup (141 KB of LDS) must get a CU before the caller's V'[A2 | b] grid fills
@@ -743,13 +657,9 @@ int lsq_cqr_alloc(lsq_ctx *c, CqrWork *w, int M) {
     LSQ_HIP(hipEventCreateWithFlags(&w->ev_lu, hipEventDisableTiming));
     LSQ_TRY(lsq_set_lds(c, (const void *)k_cqr_pass<0>, CQ_LDS));
     LSQ_TRY(lsq_set_lds(c, (const void *)k_cqr_pass<1>, CQ_LDS));
-    LSQ_TRY(lsq_set_lds(c, (const void *)k_cqr_pass<2>, CQ_LDS));
     LSQ_TRY(lsq_set_lds(c, (const void *)k_cqr_pass<1, true>, CQ_LDS));
-    LSQ_TRY(lsq_set_lds(c, (const void *)k_cqr_pass<2, true>, CQ_LDS));
     LSQ_TRY(lsq_set_lds(c, (const void *)k_cqr_factor<1>, CQ_LDS));
-    LSQ_TRY(lsq_set_lds(c, (const void *)k_cqr_factor<2>, CQ_LDS));
     LSQ_TRY(lsq_set_lds(c, (const void *)k_cqr_top, CQ_LDS_LU));
-    LSQ_TRY(lsq_set_lds(c, (const void *)k_cqr_tw, CQ_LDS_TW));
     LSQ_TRY(lsq_set_lds(c, (const void *)k_cqr_tw_q1, CQ_LDS_TW_Q1));
     w->ready = true;
     return LSQ_OK;
@@ -757,113 +667,51 @@ int lsq_cqr_alloc(lsq_ctx *c, CqrWork *w, int M) {
 
 void lsq_cqr_free(CqrWork *w) {
     if (!w || !w->ready) return;
-    hipFree(w->Gp); hipFree(w->G); hipFree(w->G2); hipFree(w->R1); hipFree(w->Binv); hipFree(w->Minv); hipFree(w->R2inv); hipFree(w->Gq1); hipFree(w->Gq2); hipFree(w->gcnt); hipFree(w->S); hipFree(w->SR);
+    hipFree(w->Gp); hipFree(w->G); hipFree(w->G2); hipFree(w->R1); hipFree(w->Binv); hipFree(w->Minv); hipFree(w->R2inv); hipFree(w->S); hipFree(w->SR);
     hipEventDestroy(w->ev_q); hipEventDestroy(w->ev_lu); hipEventDestroy(w->ev_first); hipEventDestroy(w->ev_panel);
     w->side = w->ahead = nullptr;          // (the context's)
     w->ready = false;
 }
 
-// The Q1 form (default since round 6; LSQ_QR_CQR_PASS2=1 restores the three-pass panel of rounds 2-5 for A/B): read per call.
-bool lsq_cqr_q1form() { return getenv("LSQ_QR_CQR_PASS2") == nullptr; }
-
-// MEASURED AND NOT TAKEN (round 6, profiles/r06/ab_c3_hier.txt): with the group sums k_cqr_pass<1> takes 42 instead of 24 us,
-// k_cqr_top 69 instead of 49, the Gram-forming update 68 instead of 62 -- the agent-scope stores of the partials, the last
-// arrivers' uncached re-reads and four rounds of loads in every consumer cost more than the two 9-19 us reduce launches they
-// replace: C3 7.38 ms against 6.83.  Kept behind LSQ_QR_HIER=1 (the GPU suite passes with it).
-bool lsq_cqr_hier(int nslab) {
-    return lsq_cqr_q1form() && nslab <= CQ_GS * CQ_HIER_MAX_GROUPS && getenv("LSQ_QR_HIER") != nullptr;
-}
-
+// Pass 0 (unless the previous panel's update left the Gram partials), reduce, pass 1 on ps -- the panel is then DONE on that
+// stream: Q1 is in Vb and the caller's V'[A2 | b] product may start.  The Gram reduce of pass 1's partials and everything that
+// hangs on G2 (R2, the kernel of the block reflector, inv(B), S R) run on the side stream beside that product; lsq_cqr_tw waits
+// for them (ev_lu).  (Group-level Gram sums in place of the reduce launches measured slower and were retired:
+// profiles/r06/ab_c3_hier.txt.)
 int lsq_cqr_panel(lsq_ctx *c, CqrWork *w, double *A, int M, int c0, double *Vb, int ldv, int *d_err, hipStream_t ps,
-                  bool gram_ready, bool hier, double *Vs) {
+                  bool gram_ready, double *Vs) {
     const int rows = M - c0, nslab = (rows + CQ_RS - 1) / CQ_RS;
-    const bool pre = ps == w->ahead && !getenv("LSQ_QR_AHEAD_REDUNDANT");     // one factor kernel instead of one factor per workgroup
-    const bool q1 = lsq_cqr_q1form();
-    w->q1form = q1;
+    const bool pre = ps == w->ahead;                          // one factor kernel instead of one factor per workgroup
     const int lu_only = getenv("LSQ_QR_TOP_LU") ? 1 : 0;      // (A/B: the modified LU for every panel, as in rounds 2-5)
-    if (hier && q1 && !pre) {
-        // NO reduce launches (cq_group_reduce): the producers of the Gram partials leave group sums, the consumers add them
-        const int ng = (nslab + CQ_GS - 1) / CQ_GS;
-        if (!gram_ready)
-            LSQ_LAUNCH(k_cqr_pass<0>, dim3(nslab), dim3(256), CQ_LDS, ps, A, M, c0, rows, (const double *)nullptr, w->Gp,
-                               w->R1, Vb, ldv, d_err, 0, 0, w->Gq1, w->gcnt);
-        LSQ_LAUNCH(k_cqr_pass<1>, dim3(nslab), dim3(256), CQ_LDS, ps, A, M, c0, rows, (const double *)w->Gq1, w->Gp,
-                           w->R1, Vb, ldv, d_err, 1, ng, w->Gq2, w->gcnt, Vs);
-        LSQ_HIP(hipGetLastError());
-        LSQ_HIP(hipEventRecord(w->ev_q, ps));
-        LSQ_HIP(hipStreamWaitEvent(w->side, w->ev_q, 0));
-        LSQ_LAUNCH(k_cqr_top, dim3(1), dim3(256), CQ_LDS_LU, w->side, (const double *)w->Gq2, (const double *)w->R1,
-                           (const double *)Vb, ldv, w->Binv, w->S, w->SR, d_err, w->R2inv, lu_only, ng);
-        LSQ_HIP(hipGetLastError());
-        LSQ_HIP(hipEventRecord(w->ev_lu, w->side));
-        return LSQ_OK;
-    }
-    // (measured and not kept, round 6 late: group sums for pass 1's Gram ALONE -- no reduce launch on the side chain, k_cqr_top adds
-    //  the <= 32 group sums -- 6.82 against 6.43 ms at C3: the last arrivers' sums at pass 1's tail cost more than the launch)
-    // (gram_ready: the update of the previous panel left the Gram partials of this panel's slabs in w->Gp itself)
     if (!gram_ready)
         LSQ_LAUNCH(k_cqr_pass<0>, dim3(nslab), dim3(256), CQ_LDS, ps, A, M, c0, rows, (const double *)nullptr, w->Gp,
-                           w->R1, Vb, ldv, d_err, 0);
+                           w->R1, Vb, ldv, d_err);
     LSQ_LAUNCH(k_cqr_reduce, dim3(256), dim3(256), 0, ps, (const double *)w->Gp, nslab, w->G);
     if (pre) {
-        // (LSQ_QR_FACTOR_LDS: an LDS reservation beyond what the kernel uses -- with more than 160 - 84 KB it cannot share a CU
-        //  with a workgroup of the look-ahead's update (84 KB reserved) and is placed on a free one)
-        static const size_t flds = [] { const char *e = getenv("LSQ_QR_FACTOR_LDS"); return e ? (size_t)atoi(e) : (size_t)0; }();
-        const size_t fl = std::max(CQ_LDS, flds);
-        if (fl > CQ_LDS) LSQ_TRY(lsq_set_lds(c, (const void *)k_cqr_factor<1>, fl));
-        LSQ_LAUNCH(k_cqr_factor<1>, dim3(1), dim3(256), fl, ps, (const double *)w->G, w->Minv, w->R1, d_err);
+        LSQ_LAUNCH(k_cqr_factor<1>, dim3(1), dim3(256), CQ_LDS, ps, (const double *)w->G, w->Minv, w->R1, d_err);
         LSQ_LAUNCH((k_cqr_pass<1, true>), dim3(nslab), dim3(256), CQ_LDS, ps, A, M, c0, rows, (const double *)w->Minv, w->Gp,
-                           w->R1, Vb, ldv, d_err, q1 ? 1 : 0, 0, (double *)nullptr, (unsigned *)nullptr, q1 ? Vs : nullptr);
+                           w->R1, Vb, ldv, d_err, Vs);
     } else
         LSQ_LAUNCH(k_cqr_pass<1>, dim3(nslab), dim3(256), CQ_LDS, ps, A, M, c0, rows, (const double *)w->G, w->Gp,
-                           w->R1, Vb, ldv, d_err, q1 ? 1 : 0, 0, (double *)nullptr, (unsigned *)nullptr, q1 ? Vs : nullptr);
-    if (q1) {
-        // Q1 form: the panel is DONE on this stream -- Q1 is in Vb, the caller's V'[A2 | b] product may start.  The Gram reduce of
-        // pass 1's partials and everything that hangs on G2 (R2, the 64-step LU of Q_top, inv(B), S R) run on the side stream
-        // beside that product; k_cqr_tw_q1 waits for them (ev_lu).
-        LSQ_HIP(hipGetLastError());
-        LSQ_HIP(hipEventRecord(w->ev_q, ps));
-        LSQ_HIP(hipStreamWaitEvent(w->side, w->ev_q, 0));
-        LSQ_LAUNCH(k_cqr_reduce, dim3(256), dim3(256), 0, w->side, (const double *)w->Gp, nslab, w->G2);
-        LSQ_LAUNCH(k_cqr_top, dim3(1), dim3(256), CQ_LDS_LU, w->side, (const double *)w->G2, (const double *)w->R1,
-                           (const double *)Vb, ldv, w->Binv, w->S, w->SR, d_err, w->R2inv, lu_only, 0);
-        LSQ_HIP(hipGetLastError());
-        LSQ_HIP(hipEventRecord(w->ev_lu, w->side));
-        return LSQ_OK;
-    }
-    LSQ_LAUNCH(k_cqr_reduce, dim3(256), dim3(256), 0, ps, (const double *)w->Gp, nslab, w->G2);
+                           w->R1, Vb, ldv, d_err, Vs);
     LSQ_HIP(hipGetLastError());
-    // everything that hangs on the top 64 rows (the 64-step LU among it) runs on the side stream from here on, beside
-    // pass 2 and the caller's V'[A2 | b] product
     LSQ_HIP(hipEventRecord(w->ev_q, ps));
     LSQ_HIP(hipStreamWaitEvent(w->side, w->ev_q, 0));
+    LSQ_LAUNCH(k_cqr_reduce, dim3(256), dim3(256), 0, w->side, (const double *)w->Gp, nslab, w->G2);
     LSQ_LAUNCH(k_cqr_top, dim3(1), dim3(256), CQ_LDS_LU, w->side, (const double *)w->G2, (const double *)w->R1,
-                       (const double *)(A + (size_t)c0 * M + c0), M, w->Binv, w->S, w->SR, d_err, (double *)nullptr, lu_only, 0);
-    LSQ_HIP(hipEventRecord(w->ev_lu, w->side));
-    if (pre) {
-        LSQ_LAUNCH(k_cqr_factor<2>, dim3(1), dim3(256), CQ_LDS, ps, (const double *)w->G2, w->Minv + 4096, w->R1, d_err);
-        LSQ_LAUNCH((k_cqr_pass<2, true>), dim3(nslab), dim3(256), CQ_LDS, ps, A, M, c0, rows, (const double *)(w->Minv + 4096), w->Gp,
-                           w->R1, Vb, ldv, d_err, 0);
-    } else
-        LSQ_LAUNCH(k_cqr_pass<2>, dim3(nslab), dim3(256), CQ_LDS, ps, A, M, c0, rows, (const double *)w->G2, w->Gp,
-                           w->R1, Vb, ldv, d_err, 0);
+                       (const double *)Vb, ldv, w->Binv, w->S, w->SR, d_err, w->R2inv, lu_only);
     LSQ_HIP(hipGetLastError());
+    LSQ_HIP(hipEventRecord(w->ev_lu, w->side));
     return LSQ_OK;
 }
 
 int lsq_cqr_tw(lsq_ctx *c, CqrWork *w, const double *W, int ncolsB, double *A, int M, int c0, int cend, int n,
-               double *rhs, double *Vb, int ldv, double *W2, double *W2s) {
+               double *rhs, double *W2, double *W2s) {
     LSQ_HIP(hipStreamWaitEvent(c->stream, w->ev_lu, 0));
     const int ncols = ncolsB - 64;
-    if (w->q1form) {
-        LSQ_LAUNCH(k_cqr_tw_q1, dim3(std::max(1, (ncols + TQ_NC - 1) / TQ_NC) + 1), dim3(256), CQ_LDS_TW_Q1, c->stream, W, ncolsB,
-                           (const double *)w->Binv, (const double *)w->S, (const double *)w->SR, (const double *)w->R2inv, A, M, c0, cend,
-                           n, rhs, W2, W2s);
-        LSQ_HIP(hipGetLastError());
-        return LSQ_OK;
-    }
-    LSQ_LAUNCH(k_cqr_tw, dim3(std::max(1, (ncols + 63) / 64) + 1), dim3(256), CQ_LDS_TW, c->stream, W, ncolsB,
-                       (const double *)w->Binv, (const double *)w->S, (const double *)w->SR, A, M, c0, cend, n, rhs, Vb, ldv, W2);
+    LSQ_LAUNCH(k_cqr_tw_q1, dim3(std::max(1, (ncols + TQ_NC - 1) / TQ_NC) + 1), dim3(256), CQ_LDS_TW_Q1, c->stream, W, ncolsB,
+                       (const double *)w->Binv, (const double *)w->S, (const double *)w->SR, (const double *)w->R2inv, A, M, c0, cend,
+                       n, rhs, W2, W2s);
     LSQ_HIP(hipGetLastError());
     return LSQ_OK;
 }

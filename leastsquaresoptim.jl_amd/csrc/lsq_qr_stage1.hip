@@ -491,12 +491,12 @@ k_qr1_vtb(const double *__restrict__ Vb, int ldv, const double *__restrict__ A, 
 //   leave in 128-byte pieces.  Chunks of the next V3_D steps are in flight (register ring).  The four waves of a workgroup
 //   take neighbouring 32-column groups over the SAME rows, so that three of their four reads of V hit the CU's L1; workgroups
 //   of one k slice sit behind one L2 (slice = blockIdx % kslices).
-// SWZ (round 6, late): the full chunks of V come from its fragment-order copy Vs (lsq_cqr_vs_index, written by pass 1 of the Q1
-// form): eight loads of 1 KB contiguous per chunk instead of eight in which every lane reads 32 bytes of its own column -- a load
-// costs the MFMA stream about two clocks per (4-lane group, cache line) pair it touches, 64 against 16 here
+// SWZ (round 6, late): the full chunks of V come from its fragment-order copy Vs (lsq_cqr_vs_index, written by pass 1 of the
+// CholeskyQR panel): eight loads of 1 KB contiguous per chunk instead of eight in which every lane reads 32 bytes of its own
+// column -- a load costs the MFMA stream about two clocks per (4-lane group, cache line) pair it touches, 64 against 16 here
 // (profiles/r06/ab_c3_vtb_overlap.txt, section 4).  The ragged last chunk still reads Vb.
 constexpr int V3_D = 3;
-template <int DBG, bool SWZ = false>
+template <bool SWZ = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_qr1_vtb_w(const double *__restrict__ Vb, int ldv, const double *__restrict__ A, int M, int c0, int cend, int n,
             const double *__restrict__ rhs, int ncolsB, int kslices, double *__restrict__ Wp, int tile0,
@@ -542,7 +542,6 @@ k_qr1_vtb_w(const double *__restrict__ Vb, int ldv, const double *__restrict__ A
             for (int s = 0; s < 4; ++s) bf[it][s] = pv[it * vstep + R + s];
     };
     auto chunk = [&](double (*af)[4], double (*bf)[4]) {
-        if (DBG == 1) { acc[0][0][0] += af[0][0] * bf[0][0] + af[1][3] * bf[3][3]; return; }
 #pragma unroll
         for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -869,13 +868,15 @@ typedef double u3_d2 __attribute__((ext_vector_type(2), aligned(8)));     // two
 // same bits) -- row group rg of this panel is slab rg - 1 of the next (its first 64 rows become rows of R).  The other
 // workgroups take columns jbeg..jend as before (the caller passes jbeg >= 64).
 // SWZ: W2 is read from its fragment-order copy (lsq_cqr_w2s_index: 1 KB contiguous per load instruction instead of 64 pieces of
-// 32 bytes -- the pieces cost the MFMA stream four times as many clocks, lsq_qr_cholqr.h); W2 then points at that copy.
-template <int DBG, bool GRAM = false, bool SWZ = false>     // DBG 0: the product; 1: no MFMAs (memory side alone); 2: no A2 traffic (MFMA side alone) -- timing experiments only
+// 32 bytes -- the pieces cost the MFMA stream four times as many clocks, lsq_qr_cholqr.h); W2 then points at that copy.  The
+// CholeskyQR panels always have that copy, so GRAM comes with SWZ; the Householder-step panels take neither.
+template <bool GRAM = false, bool SWZ = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_qr1_update_w(const double *__restrict__ Vb, int ldv, double *__restrict__ A, int M, int c0, int cend, int n,
                double *__restrict__ rhs, int ncols /* n - cend + 1 */, const double *__restrict__ W2, int jbeg, int jend, int tpw,
-               double *gram_out = nullptr, double *gram_q = nullptr /* group sums too (cq_group_reduce) */, unsigned *gram_cnt = nullptr,
+               double *gram_out = nullptr,
                int flat_g = 0 /* > 0: that many workgroups share the (row group, tile pair) units evenly, see qr1_update_wave */) {
+    static_assert(SWZ || !GRAM, "the Gram-forming update reads W2 in fragment order");
     extern __shared__ __attribute__((aligned(16))) double u3_qs[];      // GRAM: the slab image [col][row], CQ_QST apart
     const int rows = M - c0;
     const int nrg = (rows + Q2_NB - 1) / Q2_NB;         // row groups of 64 rows: waves 0,1 the upper half, 2,3 the lower
@@ -980,10 +981,7 @@ k_qr1_update_w(const double *__restrict__ Vb, int ldv, double *__restrict__ A, i
     };
     auto fetch_a = [&](int t, double *at) {
         const int jj = jfirst + 32 * t;
-        if (DBG == 2) {
-#pragma unroll
-            for (int r = 0; r < 8; ++r) at[r] = 0.0;
-        } else if (rfull && jj + 16 <= ncolsA) {
+        if (rfull && jj + 16 <= ncolsA) {
             const double *pa = A + (size_t)(cend + jj + kq) * M + c0 + row0;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -1005,8 +1003,6 @@ k_qr1_update_w(const double *__restrict__ Vb, int ldv, double *__restrict__ A, i
     auto tile = [&](int t, const double *wf, const double *at) {
         const int jj = jfirst + 32 * t;
         v4d_qr c00 = {0.0, 0.0, 0.0, 0.0}, c01 = c00, c10 = c00, c11 = c00;       // [row tile][k half]: four independent chains
-        if (DBG == 1) { c00[0] = wf[0] * v0[0]; c10[0] = wf[1] * v1[1]; }
-        else
 #pragma unroll
         for (int s = 0; s < 16; s += 2) {
             c00 = __builtin_amdgcn_mfma_f64_16x16x4f64(wf[s], v0[s], c00, 0, 0, 0);
@@ -1014,12 +1010,7 @@ k_qr1_update_w(const double *__restrict__ Vb, int ldv, double *__restrict__ A, i
             c01 = __builtin_amdgcn_mfma_f64_16x16x4f64(wf[s + 1], v0[s + 1], c01, 0, 0, 0);
             c11 = __builtin_amdgcn_mfma_f64_16x16x4f64(wf[s + 1], v1[s + 1], c11, 0, 0, 0);
         }
-        if (DBG == 2) {
-            double sacc = 0.0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) sacc += (c00[r] + c01[r]) + (c10[r] + c11[r]);
-            if (sacc == 1.2345e300) rhs[0] = sacc;      // (keeps the products alive)
-        } else if (rfull && jj + 16 <= ncolsA) {
+        if (rfull && jj + 16 <= ncolsA) {
             double *pa = A + (size_t)(cend + jj + kq) * M + c0 + row0;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -1080,13 +1071,7 @@ k_qr1_update_w(const double *__restrict__ Vb, int ldv, double *__restrict__ A, i
     if (GRAM && narrow) {
         const int rg = bid;
         __syncthreads();                               // the slab's 64 x 64 block of the next panel is in the image
-        if (rg >= 1 && gram_out) {                     // (uniform over the workgroup)
-            if (gram_q) {
-                cq_slab_gram<true>(u3_qs, gram_out + (size_t)(rg - 1) * 4096, tid);
-                cq_group_reduce(gram_out, gram_q, gram_cnt, rg - 1, nrg - 1, tid);
-            } else
-                cq_slab_gram(u3_qs, gram_out + (size_t)(rg - 1) * 4096, tid);
-        }
+        if (rg >= 1 && gram_out) cq_slab_gram(u3_qs, gram_out + (size_t)(rg - 1) * 4096, tid);     // (uniform over the workgroup)
     }
 }
 
@@ -1102,33 +1087,37 @@ k_qr1_extract(const double *__restrict__ A, int M, int n, const double *__restri
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) rhs2[i] = rhs[i];
 }
 
-// launches the wave-private update (default since round 5; LSQ_QR_UPDATE_W=0: false, the caller launches k_qr1_update; 2 / 3: the
-// timing experiments DBG 1 / 2 -- wrong results).  All read per call.
+// LSQ_QR_UPDATE_W=0 / LSQ_QR_VTB_W=0: the LDS-staged trailing kernels of round 4 (k_qr1_update / k_qr1_vtb), which sum in
+// another order -- the tests' independent reference for the wave-private ones.  Read per call (the tests flip them).
+static bool qr_env_zero(const char *name) {
+    const char *e = getenv(name);
+    return e && atoi(e) == 0;
+}
+
+// launches the wave-private update (default since round 5; with LSQ_QR_UPDATE_W=0 *taken is false and the caller launches
+// k_qr1_update).
 // gram_out (or null): the launch also updates trailing columns 0..63 -- the next panel -- in nrg workgroups of their own and leaves
-// the Gram partials of the next panel's slabs there (k_qr1_update_w<0, true>); the caller then passes jbeg >= 64 (jbeg == jend:
-// those workgroups alone).
+// the Gram partials of the next panel's slabs there (k_qr1_update_w<true, true>); the caller then passes jbeg >= 64 (jbeg == jend:
+// those workgroups alone).  W2s (or null): W2 in fragment order too (lsq_cqr_w2s_index), which the kernel then reads; gram_out
+// needs it.
 static int qr1_update_wave(lsq_ctx *c, const double *Vb, int ldv, double *A, int M, int c0, int cend, int n, double *rhs,
                            int ncols, const double *W2, bool *taken, int jbeg = 0, int jend = -1, bool beside_passes = false,
-                           double *gram_out = nullptr, double *gram_q = nullptr, unsigned *gram_cnt = nullptr,
-                           const double *W2s = nullptr /* W2 in fragment order too (lsq_cqr_w2s_index): the kernel reads that copy */) {
-    const char *e = getenv("LSQ_QR_UPDATE_W");
-    const int mode = e ? atoi(e) : 1;
-    *taken = mode != 0;
-    if (mode == 0) return LSQ_OK;
+                           double *gram_out = nullptr, const double *W2s = nullptr) {
+    *taken = !qr_env_zero("LSQ_QR_UPDATE_W");
+    if (!*taken) return LSQ_OK;
+    if (gram_out && !W2s) { lsq_set_error("qr: the Gram-forming update needs W2 in fragment order"); return LSQ_EARG; }
     if (jend < 0) jend = ncols;
     if (jbeg >= jend && !gram_out) return LSQ_OK;
     const int rows = M - c0, nrg = (rows + Q2_NB - 1) / Q2_NB;
     // 32-column tile pairs per workgroup: as many as leave one workgroup per CU, at most 32 -- a wave's V fragment then serves
     // many tiles (measured at C3, all panels: 32 pairs 57.8 us, 16 58.9, 8 61.0, 4 62.3; a rule that keeps two workgroups per
     // CU 60.1)
-    const char *t = getenv("LSQ_QR_UPDATE_TPW");
     const int npair = (std::max(jend - jbeg, 0) + 31) / 32, want = std::max(1, c->num_cus / nrg);
-    int tpw = t ? std::max(1, atoi(t)) : std::max(2, std::min(beside_passes ? 64 : 32, (npair + want - 1) / want));
+    int tpw = std::max(2, std::min(beside_passes ? 64 : 32, (npair + want - 1) / want));
     int ncg = (npair + tpw - 1) / tpw;
-    // beside the next panel's passes (look-ahead): ONE workgroup per CU, by an LDS reservation it does not use -- two of them
-    // fill a CU's registers (242 VGPRs per wave) and the pass workgroups (75 KB of LDS, 4 waves) would wait for them to end
-    const char *le = getenv("LSQ_QR_UPDATE_LDS");
-    size_t lds = beside_passes ? (le ? (size_t)atoi(le) : (size_t)84 * 1024) : 0;
+    // beside the next panel's passes (look-ahead): ONE workgroup per CU, by an 84 KB LDS reservation it does not use -- two of
+    // them fill a CU's registers (242 VGPRs per wave) and the pass workgroups (75 KB of LDS, 4 waves) would wait for them to end
+    size_t lds = beside_passes ? (size_t)84 * 1024 : 0;
     if (gram_out) lds = std::max(lds, (size_t)Q2_NB * CQ_QST * sizeof(double));
     // FLAT MAPPING (round 6, later): with one workgroup per (row group, column group) the grid is a multiple of nrg, and once
     // nrg does not divide the CUs some CUs run a workgroup more than the others -- at 18432 rows (288 row groups, 576
@@ -1143,7 +1132,7 @@ static int qr1_update_wave(lsq_ctx *c, const double *Vb, int ldv, double *A, int
     const char *fe = getenv("LSQ_QR_UPDATE_FLAT");
     const long long units = (long long)nrg * npair;
     int flat_g = 0;
-    if (!(fe && atoi(fe) == 0) && !t && units > 0) {
+    if (!(fe && atoi(fe) == 0) && units > 0) {
         const int cap = beside_passes ? 64 : 32;
         double t_rect = 1e30;
         int tpw_rect = tpw;
@@ -1156,12 +1145,10 @@ static int qr1_update_wave(lsq_ctx *c, const double *Vb, int ldv, double *A, int
         }
         const int per_cu = fe ? std::max(1, atoi(fe)) : (beside_passes || units <= (long long)cap * c->num_cus ? 1 : 2);
         const double t_flat = (double)units / c->num_cus + 0.5 * per_cu + 1.5;
-        // (beside the next panel's passes: LSQ_QR_UPDATE_SPARE CUs, default 2, are left without a workgroup of this launch --
-        //  the look-ahead's one-workgroup kernels find a quieter CU: 7.41 -> 7.34 ms on LM's stacked C3 operand, 24000 x 2048
-        //  8.59 -> 8.46; forcing the factor kernel onto a FREE CU by an LDS reservation, LSQ_QR_FACTOR_LDS=102400, loses 3 %;
-        //  profiles/r06/ab_c3_lookahead_spare_cus.txt)
-        static const int spare = [] { const char *e = getenv("LSQ_QR_UPDATE_SPARE"); return e ? std::max(0, atoi(e)) : 2; }();
-        const int sp = beside_passes ? std::min(spare, c->num_cus / 2) : 0;
+        // (beside the next panel's passes: 2 CUs are left without a workgroup of this launch -- the look-ahead's one-workgroup
+        //  kernels find a quieter CU: 7.41 -> 7.34 ms on LM's stacked C3 operand, 24000 x 2048 8.59 -> 8.46; forcing the factor
+        //  kernel onto a FREE CU by an LDS reservation loses 3 %; profiles/r06/ab_c3_lookahead_spare_cus.txt)
+        const int sp = beside_passes ? std::min(2, c->num_cus / 2) : 0;
         if (fe || sp > 0 || t_flat < 0.97 * t_rect)
             flat_g = (int)std::max(1LL, std::min((long long)per_cu * c->num_cus - sp, units / 2));
         else { tpw = tpw_rect; ncg = (npair + tpw - 1) / tpw; }
@@ -1170,19 +1157,14 @@ static int qr1_update_wave(lsq_ctx *c, const double *Vb, int ldv, double *A, int
     auto go = [&](auto kern) -> int {
         if (lds > 48 * 1024) LSQ_TRY(lsq_set_lds(c, (const void *)kern, lds));
         LSQ_LAUNCH(kern, dim3(grid), dim3(256), lds, c->stream, Vb, ldv, A, M, c0, cend, n, rhs, ncols, W2, jbeg, jend, tpw, gram_out,
-                   gram_q, gram_cnt, flat_g);
+                   flat_g);
         LSQ_HIP(hipGetLastError());
         return LSQ_OK;
     };
-    if (W2s && mode == 1) {
-        W2 = W2s;
-        if (gram_out) return go(k_qr1_update_w<0, true, true>);
-        return go(k_qr1_update_w<0, false, true>);
-    }
-    if (gram_out) return go(k_qr1_update_w<0, true>);
-    if (mode == 2) return go(k_qr1_update_w<1>);
-    if (mode == 3) return go(k_qr1_update_w<2>);
-    return go(k_qr1_update_w<0>);
+    if (!W2s) return go(k_qr1_update_w<>);
+    W2 = W2s;
+    if (gram_out) return go(k_qr1_update_w<true, true>);
+    return go(k_qr1_update_w<false, true>);
 }
 
 static void qr2_free(void *p) {
@@ -1200,24 +1182,20 @@ static void qr2_free(void *p) {
 // about four workgroups per CU whatever the width of the trailing matrix.  (Until round 5 the count was fixed by the WIDEST
 // panel -- 31 at C3 -- so that the last panels ran 62 workgroups of 15 dependent slabs each: 33 us for 1 % of the flops.)
 static int qr1_vtb_slices(const lsq_ctx *c, const Qr2Work *q, int rows, int nt, int ntile) {
-    const char *e = getenv("LSQ_QR_VTB_KSMAX");
-    const int ksmax = e ? atoi(e) : 64;
-    // (rounded DOWN, and four slots kept free: k_cqr_top holds a CU's LDS on the side stream while this grid runs -- a
-    //  workgroup over the resident 4 per CU waits for a whole second round: 127 against 102 us at 30 tiles x 35 slices)
-    int ks = ksmax > 0 ? std::min(ksmax, (4 * c->num_cus - 4) / std::max(1, nt)) : q->kslices;
+    // (at most 64; rounded DOWN, and four slots kept free: k_cqr_top holds a CU's LDS on the side stream while this grid runs --
+    //  a workgroup over the resident 4 per CU waits for a whole second round: 127 against 102 us at 30 tiles x 35 slices)
+    int ks = std::min(64, (4 * c->num_cus - 4) / std::max(1, nt));
     ks = std::min(ks, q->wp_slots / std::max(1, ntile));
     ks = std::min(ks, (rows + 4 * Q2_KC - 1) / (4 * Q2_KC));
     return std::max(1, ks);
 }
 
-// V'[A2 | b] partials by the wave-private kernel (default; LSQ_QR_VTB_W=0: k_qr1_vtb; 2: timing experiment without MFMAs).
+// V'[A2 | b] partials by the wave-private kernel (default; LSQ_QR_VTB_W=0: k_qr1_vtb).
 // Returns the number of k slices written (for k_qr1_wreduce), or -1 if the launch failed.
 static int qr1_vtb_launch(lsq_ctx *c, Qr2Work *q, const double *Vb, int ldv, const double *A, int M, int c0, int cend, int n,
                           const double *rhs, int ncolsB, int tile0, const double *Vs = nullptr /* V in fragment order too */) {
     const int ntile = (ncolsB + Q2_NB - 1) / Q2_NB, rows = M - c0;
-    const char *e = getenv("LSQ_QR_VTB_W");
-    const int mode = e ? atoi(e) : 1;
-    if (mode == 0) {
+    if (qr_env_zero("LSQ_QR_VTB_W")) {
         const int ks = qr1_vtb_slices(c, q, rows, ntile - tile0, ntile);
         LSQ_LAUNCH(k_qr1_vtb, dim3((ntile - tile0) * ks), dim3(256), 0, c->stream, Vb, ldv, A, M, c0, cend, n, rhs, ncolsB, ks,
                            q->Wp, tile0);
@@ -1226,9 +1204,7 @@ static int qr1_vtb_launch(lsq_ctx *c, Qr2Work *q, const double *Vb, int ldv, con
     // workgroups of 4 waves x 32 columns; ONE per CU (measured at C3, average over the panels: 56.2 us; two per CU -- what
     // the registers allow -- 59.0; four queued 71.1; k_qr1_vtb 64.0)
     const int ncgrp = (ncolsB - tile0 * Q2_NB + 127) / 128;
-    const char *k = getenv("LSQ_QR_VTB_WGS");
-    const int per_cu = k ? std::max(1, atoi(k)) : 1;
-    int ks = std::max(1, (per_cu * c->num_cus - 2) / std::max(1, ncgrp));
+    int ks = std::max(1, (c->num_cus - 2) / std::max(1, ncgrp));
     ks = std::min(ks, 128);
     ks = std::min(ks, q->wp_slots / std::max(1, ntile));
     ks = std::max(1, std::min(ks, (rows + 63) / 64));
@@ -1236,20 +1212,13 @@ static int qr1_vtb_launch(lsq_ctx *c, Qr2Work *q, const double *Vb, int ldv, con
     // these workgroups on a CU, so the grid (<= CUs - 2 workgroups) leaves whole CUs free -- and k_cqr_top (141 KB of LDS, on
     // the high-priority side stream beside this product) can only be placed on one of THOSE: it runs alone on its CU instead of
     // sharing issue slots with a product workgroup (measured: 47 us alone, 78 us beside one).
-    const char *le = getenv("LSQ_QR_VTB_LDS");
-    const size_t lds = per_cu == 1 ? (le ? (size_t)atoi(le) : (size_t)84 * 1024) : 0;
-    if (mode == 2) {
-        if (lds > 48 * 1024 && lsq_set_lds(c, (const void *)k_qr1_vtb_w<1>, lds) != LSQ_OK) return -1;
-        LSQ_LAUNCH(k_qr1_vtb_w<1>, dim3(ncgrp * ks), dim3(256), lds, c->stream, Vb, ldv, A, M, c0, cend, n, rhs, ncolsB, ks, q->Wp, tile0);
-    } else if (Vs) {
-        if (lds > 48 * 1024 && lsq_set_lds(c, (const void *)k_qr1_vtb_w<0, true>, lds) != LSQ_OK) return -1;
-        LSQ_LAUNCH((k_qr1_vtb_w<0, true>), dim3(ncgrp * ks), dim3(256), lds, c->stream, Vb, ldv, A, M, c0, cend, n, rhs, ncolsB, ks, q->Wp,
-                   tile0, Vs);
-    } else {
-        if (lds > 48 * 1024 && lsq_set_lds(c, (const void *)k_qr1_vtb_w<0>, lds) != LSQ_OK) return -1;
-        LSQ_LAUNCH(k_qr1_vtb_w<0>, dim3(ncgrp * ks), dim3(256), lds, c->stream, Vb, ldv, A, M, c0, cend, n, rhs, ncolsB, ks, q->Wp, tile0);
-    }
-    return hipGetLastError() == hipSuccess ? ks : -1;
+    const size_t lds = (size_t)84 * 1024;
+    auto go = [&](auto kern) -> int {
+        if (lsq_set_lds(c, (const void *)kern, lds) != LSQ_OK) return -1;
+        LSQ_LAUNCH(kern, dim3(ncgrp * ks), dim3(256), lds, c->stream, Vb, ldv, A, M, c0, cend, n, rhs, ncolsB, ks, q->Wp, tile0, Vs);
+        return hipGetLastError() == hipSuccess ? ks : -1;
+    };
+    return Vs ? go(k_qr1_vtb_w<true>) : go(k_qr1_vtb_w<>);
 }
 
 static bool qr2_applies(int M, int n) {
@@ -1361,39 +1330,26 @@ static int qr2_factor_core(lsq_solver *s, double *A, double *rhs, int M, int n, 
     const bool cq_ok = !q->no_cholqr && !getenv("LSQ_QR1_NO_CHOLQR") && !getenv("LSQ_QR_ALWAYS_PIVOT");
     q->cholqr_used = false;
     // LOOK-AHEAD (round 5): once panel k's W2 is known, the NEXT panel's 64 columns are updated first and its passes run on
-    // their own stream beside the update of the other trailing columns; its Q goes to the second V buffer.  (Round 3 built
+    // their own stream beside the update of the other trailing columns; its Q1 goes to the second V buffer.  (Round 3 built
     // this on LDS-staged update kernels: pass and update workgroups fought for the CUs' LDS, both stretched, 8.0 against
     // 7.55 ms.  The wave-private update holds no LDS.)  Only with the wave-private update (it takes a column range).
+    // Round 6: the panel's chain is already short and runs beside the V'[A2 | b] product, so by default a panel is factored
+    // ahead only if it has more 64-row slabs than the device has CUs: its passes no longer fit one round of workgroups, the chain
+    // grows by a half and there it pays to hide it -- 20000 x 1000 3.32 -> 3.04 ms, 40000 x 512 1.94 -> 1.76, 24000 x 2048
+    // 9.35 -> 8.81, LM's stacked 18432 x 2048 operand 8.32 -> 7.80 -- while C3's 16384 rows (256 slabs) are a wash and 4096 x
+    // 512, 3000 x 700, 8192 x 1024 lose 5-10 % (profiles/r06/ab_c3_lookahead_tall.txt).  LSQ_QR_LOOKAHEAD=1 factors every
+    // eligible panel ahead, =0 none.
+    const int la_min_rows = c->num_cus * CQ_RS + 1;
     const char *lae = getenv("LSQ_QR_LOOKAHEAD");
-    const char *uwe = getenv("LSQ_QR_UPDATE_W");
-    // Round 6: in the Q1 form of the panel (one pass, the rest on the side stream) the chain that the look-ahead would hide is
-    // already short and runs beside the V'[A2 | b] product; measured with it 6.82 / 7.91 ms (C3 / LM's stacked operand), without
-    // 6.77 / 7.92 -- so it is taken only where asked for (LSQ_QR_LOOKAHEAD=1) or in the three-pass form (LSQ_QR_CQR_PASS2=1).
-    // ... EXCEPT for panels with more 64-row slabs than the device has CUs (round 6, later): their passes no longer fit one round
-    // of workgroups, the chain grows by a half and there it pays to hide it.  With every panel factored ahead (no minimum of
-    // other columns) 20000 x 1000 takes 3.04 instead of 3.32 ms, 40000 x 512 1.76 / 1.94, 24000 x 2048 8.81 / 9.35, LM's stacked
-    // 18432 x 2048 operand 7.80 / 8.32 -- while C3's 16384 rows (256 slabs) are a wash (6.76 / 6.88) and 4096 x 512, 3000 x 700,
-    // 8192 x 1024 lose 5-10 % (profiles/r06/ab_c3_lookahead_tall.txt).  So in the Q1 form, unless LSQ_QR_LOOKAHEAD says otherwise,
-    // a panel is factored ahead iff it has more than num_cus * CQ_RS rows.
-    const int la_q1_min_rows = c->num_cus * CQ_RS + 1;
-    const bool la_auto = !lae && lsq_cqr_q1form();
-    const bool la_on = cq_ok && (lae ? atoi(lae) != 0 : true) && (uwe ? atoi(uwe) == 1 : true);
-    // worth it while the update of the other columns outlasts most of the passes (which run 1.5-2x slower beside it):
-    // measured at C3 7.20 -> 7.06 ms, 18432 x 2048 8.94 -> 8.22; 4096 x 512 and 3000 x 700 lose 3-5 % with it
-    const char *lmc = getenv("LSQ_QR_LOOKAHEAD_MINCOLS");
-    const int la_min_cols = lmc ? atoi(lmc) : (la_auto ? 0 : 1024);
-    const bool swz_on = !getenv("LSQ_QR_NO_SWIZZLE");
-    bool pre = false;                        // this panel was factored ahead (its Q is in vcur, ev_panel says when)
+    const bool wave_update = !qr_env_zero("LSQ_QR_UPDATE_W");
+    const bool la_on = cq_ok && wave_update && (lae ? atoi(lae) != 0 : true);
+    bool pre = false;                        // this panel was factored ahead (its Q1 is in vcur, ev_panel says when)
     // FUSED GRAM (round 6): the update of panel k forms the Gram partials of panel k + 1 (its first pass, k_cqr_pass<0>, is one
-    // launch less on every panel's chain); only the wave-private update does it (mode 1, no timing experiment)
-    const bool gram_on = cq_ok && !getenv("LSQ_QR_NO_FUSED_GRAM") && (uwe ? atoi(uwe) == 1 : true);
+    // launch less on every panel's chain); only the wave-private update does it
+    const bool gram_on = cq_ok && !getenv("LSQ_QR_NO_FUSED_GRAM") && wave_update;
     bool gram_ready = false;                 // ... and did so for the panel at hand
-    // GROUP-LEVEL GRAM SUMS (round 6, cq_group_reduce: no reduce launches; Q1 form without look-ahead) -- measured slower,
-    // LSQ_QR_HIER=1 only (lsq_cqr_hier)
-    const bool hier_on = cq_ok && (!la_on || la_auto) && getenv("LSQ_QR_HIER") != nullptr;   // (panels not factored ahead)
-    bool hier_ready = false;                 // the partials at hand came with their group sums
     double *vcur = q->Vb;
-    double *vscur = nullptr;                 // vcur's fragment-order copy (Q1 form), or null
+    double *vscur = q->Vs;                   // vcur's fragment-order copy
     for (int c0 = 0; c0 < n; c0 += Q2_NB) {
         const int nb = std::min(Q2_NB, n - c0), cend = c0 + nb;
         if (cq_ok && nb == Q2_NB && M - c0 >= 256) {
@@ -1404,13 +1360,11 @@ static int qr2_factor_core(lsq_solver *s, double *A, double *rhs, int M, int n, 
             if (pre) LSQ_HIP(hipStreamWaitEvent(c->stream, q->cq.ev_panel, 0));
             else {
                 vcur = q->Vb;
-                vscur = swz_on && lsq_cqr_q1form() ? q->Vs : nullptr;
-                const bool hier = hier_on && lsq_cqr_hier((rows + CQ_RS - 1) / CQ_RS) && (!gram_ready || hier_ready);
-                LSQ_TRY(lsq_cqr_panel(c, &q->cq, A, M, c0, vcur, ldv, q->d_err, c->stream, gram_ready, hier, vscur));
+                vscur = q->Vs;
+                LSQ_TRY(lsq_cqr_panel(c, &q->cq, A, M, c0, vcur, ldv, q->d_err, c->stream, gram_ready, vscur));
             }
             pre = false;
             gram_ready = false;
-            hier_ready = false;
             const int ncols = n - cend + 1, ncolsB = Q2_NB + ncols;
             const int ntile = (ncolsB + Q2_NB - 1) / Q2_NB;
             // (V'V, tile 0, is not formed: the basis-kernel form needs V'[A2 | b] only.  Measured and dropped in round 4: the sum
@@ -1423,30 +1377,25 @@ static int qr2_factor_core(lsq_solver *s, double *A, double *rhs, int M, int n, 
                 int g = (int)std::min<long long>((tot + 255) / 256, (long long)c->num_cus * 4);
                 LSQ_LAUNCH(k_qr1_wreduce, dim3(g), dim3(256), 0, c->stream, q->Wp, ncolsB, ks, q->W, 1);
             }
-            // (Q1 form: W2 also in the update's fragment order -- LSQ_QR_NO_SWIZZLE=1: round 5's loads, A/B)
-            const double *w2s = q->cq.q1form && swz_on ? q->W2s : nullptr;
-            LSQ_TRY(lsq_cqr_tw(c, &q->cq, q->W, ncolsB, A, M, c0, cend, n, rhs, vcur, ldv, q->W2, const_cast<double *>(w2s)));
-            // is the next panel a CholeskyQR2 panel too, with enough other columns beside it?
+            // (W2 also in the update's fragment order)
+            LSQ_TRY(lsq_cqr_tw(c, &q->cq, q->W, ncolsB, A, M, c0, cend, n, rhs, q->W2, q->W2s));
             const int c1 = cend;
             const bool next_cq = n - c1 >= Q2_NB && M - c1 >= 256;       // the next panel is a CholeskyQR panel too
-            const bool ahead = la_on && next_cq && ncols - 1 >= Q2_NB + la_min_cols && (!la_auto || M - c1 >= la_q1_min_rows);
+            const bool ahead = la_on && next_cq && (lae || M - c1 >= la_min_rows);
             double *const gram_out = gram_on && next_cq ? q->cq.Gp : nullptr;
             if (ahead) {
                 if (!q->Vb2) LSQ_HIP(hipMalloc(&q->Vb2, ((size_t)q->M * Q2_NB + 64) * sizeof(double)));
+                if (!q->Vs2) LSQ_HIP(hipMalloc(&q->Vs2, ((size_t)(q->M + 16) * Q2_NB + 64) * sizeof(double)));
                 double *vnext = vcur == q->Vb ? q->Vb2 : q->Vb;
-                double *vsnext = nullptr;
-                if (swz_on && lsq_cqr_q1form()) {
-                    if (!q->Vs2) LSQ_HIP(hipMalloc(&q->Vs2, ((size_t)(q->M + 16) * Q2_NB + 64) * sizeof(double)));
-                    vsnext = vnext == q->Vb ? q->Vs : q->Vs2;
-                }
+                double *vsnext = vnext == q->Vb ? q->Vs : q->Vs2;
                 bool tk = false;
-                if (gram_out) LSQ_TRY(qr1_update_wave(c, vcur, ldv, A, M, c0, cend, n, rhs, ncols, q->W2, &tk, Q2_NB, Q2_NB, false, gram_out, nullptr, nullptr, w2s));
-                else LSQ_TRY(qr1_update_wave(c, vcur, ldv, A, M, c0, cend, n, rhs, ncols, q->W2, &tk, 0, Q2_NB, false, nullptr, nullptr, nullptr, w2s));
+                if (gram_out) LSQ_TRY(qr1_update_wave(c, vcur, ldv, A, M, c0, cend, n, rhs, ncols, q->W2, &tk, Q2_NB, Q2_NB, false, gram_out, q->W2s));
+                else LSQ_TRY(qr1_update_wave(c, vcur, ldv, A, M, c0, cend, n, rhs, ncols, q->W2, &tk, 0, Q2_NB, false, nullptr, q->W2s));
                 LSQ_HIP(hipEventRecord(q->cq.ev_first, c->stream));
                 LSQ_HIP(hipStreamWaitEvent(q->cq.ahead, q->cq.ev_first, 0));
-                LSQ_TRY(lsq_cqr_panel(c, &q->cq, A, M, c1, vnext, M - c1, q->d_err, q->cq.ahead, gram_out != nullptr, false, vsnext));
+                LSQ_TRY(lsq_cqr_panel(c, &q->cq, A, M, c1, vnext, M - c1, q->d_err, q->cq.ahead, gram_out != nullptr, vsnext));
                 LSQ_HIP(hipEventRecord(q->cq.ev_panel, q->cq.ahead));
-                LSQ_TRY(qr1_update_wave(c, vcur, ldv, A, M, c0, cend, n, rhs, ncols, q->W2, &tk, Q2_NB, ncols, true, nullptr, nullptr, nullptr, w2s));
+                LSQ_TRY(qr1_update_wave(c, vcur, ldv, A, M, c0, cend, n, rhs, ncols, q->W2, &tk, Q2_NB, ncols, true, nullptr, q->W2s));
                 vcur = vnext;
                 vscur = vsnext;
                 pre = true;
@@ -1454,13 +1403,10 @@ static int qr2_factor_core(lsq_solver *s, double *A, double *rhs, int M, int n, 
                 const int nrt = (rows + Q2_NB - 1) / Q2_NB, nct = (ncols + Q2_NB - 1) / Q2_NB;
                 bool tk = false;
                 if (gram_out) {
-                    const bool hn = hier_on && lsq_cqr_hier((M - c1 + CQ_RS - 1) / CQ_RS);      // (the NEXT panel's slabs)
-                    LSQ_TRY(qr1_update_wave(c, vcur, ldv, A, M, c0, cend, n, rhs, ncols, q->W2, &tk, Q2_NB, ncols, false, gram_out,
-                                            hn ? q->cq.Gq1 : nullptr, hn ? q->cq.gcnt : nullptr, w2s));
+                    LSQ_TRY(qr1_update_wave(c, vcur, ldv, A, M, c0, cend, n, rhs, ncols, q->W2, &tk, Q2_NB, ncols, false, gram_out, q->W2s));
                     gram_ready = true;
-                    hier_ready = hn;
                 } else
-                LSQ_TRY(qr1_update_wave(c, vcur, ldv, A, M, c0, cend, n, rhs, ncols, q->W2, &tk, 0, -1, false, nullptr, nullptr, nullptr, w2s));
+                LSQ_TRY(qr1_update_wave(c, vcur, ldv, A, M, c0, cend, n, rhs, ncols, q->W2, &tk, 0, -1, false, nullptr, q->W2s));
                 if (!tk)
                 LSQ_LAUNCH(k_qr1_update, dim3(nrt * ((nct + Q2_UCT - 1) / Q2_UCT)), dim3(256), 0, c->stream, vcur, ldv, A, M,
                                    c0, cend, n, rhs, ncols, q->W2);

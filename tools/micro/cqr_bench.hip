@@ -25,11 +25,11 @@ int main() {
     hipMemcpyFromSymbol(t, HIP_SYMBOL(cq_tbuf), sizeof(t));
     auto us = [&](int a, int b) { return (double)(t[b] - t[a]) * 0.01; };   // wall_clock64: 100 MHz
     printf("pass0: load %.2f  gram %.2f\n", us(0, 1), us(1, 2));
-    for (int p = 1; p <= 2; ++p)
-        printf("pass%d: load G + factor + inverse %.2f  R store %.2f  slab product %.2f  write-out %.2f  gram %.2f | total %.2f\n", p,
-               us(16 * p, 16 * p + 2), us(16 * p + 2, 16 * p + 3), us(16 * p + 3, 16 * p + 4),
-               us(16 * p + 4, 16 * p + 5), us(16 * p + 5, 16 * p + 6), us(16 * p, 16 * p + 6));
-    if (t[52] > t[53] && t[53] > t[49])       // Neumann path of k_cqr_top (Q1 form, tall panel)
+    const int p = 1;
+    printf("pass1: load G + factor %.2f  R store %.2f  slab product %.2f  write-out %.2f  gram %.2f | total %.2f\n",
+           us(16 * p, 16 * p + 2), us(16 * p + 2, 16 * p + 3), us(16 * p + 3, 16 * p + 4),
+           us(16 * p + 4, 16 * p + 5), us(16 * p + 5, 16 * p + 6), us(16 * p, 16 * p + 6));
+    if (t[52] > t[53] && t[53] > t[49])       // Neumann path of k_cqr_top (tall panel)
         printf("top (Neumann): G2 + factor + R + Q_top %.2f  E, E^2, decision, S R %.2f  squaring loop + inv(B) store %.2f | total %.2f\n",
                us(48, 49), us(49, 53), us(53, 52), us(48, 52));
     else
