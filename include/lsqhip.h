@@ -64,6 +64,17 @@ int lsq_dense_create(lsq_ctx *ctx, int m, int n, lsq_mat **out);
 /* CSC pattern given once (SparseMatrixCSC with a FIXED pattern, as the reference's sparse g!
  * requires: test/nonlinearleastsquares.jl:47-86).  Builds the CSR mirror + CSC->CSR value map. */
 int lsq_csc_create(lsq_ctx *ctx, int m, int n, const int *h_colptr, const int *h_rowval, lsq_mat **out);
+/* J = blkdiag(J_1 .. J_B), every block dense mb x nb: m = B*mb, n = B*nb.  Values are addressed exactly like a CSC
+ * handle with that pattern: nzval order = [block][column][row], i.e. B column-major mb x nb blocks back to back
+ * (lsq_mat_set_values / _async / lsq_mat_values / lsq_mat_get_values / lsq_mat_refresh / lsq_mat_set_colscale).  The handle
+ * IS a CSC handle (products, column sums, LSMR(), column scaling, sharding: unchanged) that also knows its block shape:
+ * lsq_solver_create accepts it with LSQ_CHOLESKY when nb <= 64 -- J'J + diag(damp) is block-diagonal, so the normal
+ * equations of LevenbergMarquardt(Cholesky()) / Dogleg(Cholesky()) are B independent nb x nb factorisations, one pass over
+ * the values per solve, with the reference's semantics on the stacked system (one trust region, LSQ_ENOTPD at the column
+ * where the stacked dpotrf stops, LSQ_ERANK when the stacked pivoted factorisation stops early).  LSQ_QR stays refused. */
+int lsq_blockdiag_create(lsq_ctx *ctx, int nblocks, int mb, int nb, lsq_mat **out);
+/* 0 blocks for any other handle */
+int lsq_mat_blockdiag_info(const lsq_mat *J, int *nblocks, int *mb, int *nb);
 int lsq_mat_destroy(lsq_mat *J);
 int lsq_mat_size(const lsq_mat *J, int *m, int *n, long long *nnz);
 /* Upload values after a host-side g!(J, x): dense m*n column-major, or nzval in CSC order. */
@@ -212,6 +223,9 @@ int lsq_solver_qr_panel(const lsq_solver *s, int *kind);
  * 4 like 2 with the whole factorisation in ONE launch (k_chol_tiles: one resident workgroup per 64 x 64 upper tile,
  * n <= 1408; repeated as 2 if one of its bounded waits gives up) */
 int lsq_solver_chol_path(const lsq_solver *s, int *path);
+/* diagnostics of the last block solve: which path (0 none yet, 1 batched unpivoted LM, 2 batched pivoted Dogleg) and,
+ * after LSQ_ENOTPD / LSQ_ERANK, the block that decided it (else -1) */
+int lsq_solver_blockdiag_path(const lsq_solver *s, int *path, int *block);
 
 /* The fast paths above that rely on co-resident workgroups (one-launch Cholesky, pipelined triangular solves, the QR panel's slab
  * exchange + pipelined certified solve) wait with a bound; a wait that gives up makes the solve repeat itself on the

@@ -101,6 +101,8 @@ def lib():
         "lsq_d2d": (i, [vp, vp, vp, sz]),
         "lsq_dense_create": (i, [vp, i, i, pvp]),
         "lsq_csc_create": (i, [vp, i, i, c_ip, c_ip, pvp]),
+        "lsq_blockdiag_create": (i, [vp, i, i, i, pvp]),
+        "lsq_mat_blockdiag_info": (i, [vp, c_ip, c_ip, c_ip]),
         "lsq_mat_destroy": (i, [vp]),
         "lsq_mat_size": (i, [vp, c_ip, c_ip, C.POINTER(C.c_longlong)]),
         "lsq_mat_set_values": (i, [vp, c_dp]),
@@ -144,6 +146,7 @@ def lib():
         "lsq_solver_qr_path": (i, [vp, c_ip]),
         "lsq_solver_qr_panel": (i, [vp, c_ip]),
         "lsq_solver_chol_path": (i, [vp, c_ip]),
+        "lsq_solver_blockdiag_path": (i, [vp, c_ip, c_ip]),
         "lsq_solver_stats": (i, [vp, c_ip, c_ip]),
         "lsq_ctx_fallback_stats": (i, [vp, c_ip]),
         "lsq_ctx_device_info": (i, [vp, c_ip, c_ip, C.c_char_p, i]),

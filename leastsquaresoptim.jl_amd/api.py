@@ -121,14 +121,83 @@ def _is_sparse(J):
     return _sp is not None and _sp.issparse(J)
 
 
+class BlockDiagonal:
+    """J = blkdiag(J_1 .. J_B), every block dense mb x nb: the Jacobian of B independent small fits stacked into one
+    problem (m = B*mb residuals, n = B*nb parameters).  A host-side container like a scipy CSC matrix with a fixed pattern:
+    `.data` is the flat value array g_ overwrites (the sparse contract, test/nonlinearleastsquares.jl:47-86), ordered
+    [block][column][row] -- B column-major mb x nb blocks back to back, which IS the nzval order of `.tocsc()`.
+    On the device it becomes a CSC handle that knows its block shape (lsq_blockdiag_create): LSMR() is the default solver
+    (types.jl:114-127: anything not dense), Cholesky() solves the B normal-equation blocks in one pass (nb <= 64),
+    QR() is refused as for every sparse Jacobian."""
+
+    def __init__(self, nblocks, mb, nb, data=None):
+        nblocks, mb, nb = int(nblocks), int(mb), int(nb)
+        if nblocks < 1 or mb < 1 or nb < 1:
+            raise DimensionMismatch(_lib.EDIM, "BlockDiagonal needs nblocks >= 1, mb >= 1, nb >= 1 (got %d, %d, %d)"
+                                    % (nblocks, mb, nb))
+        self.nblocks, self.mb, self.nb = nblocks, mb, nb
+        self.shape = (nblocks * mb, nblocks * nb)
+        self.nnz = nblocks * mb * nb
+        if data is None:
+            self.data = np.zeros(self.nnz)
+        else:
+            d = np.ascontiguousarray(data, dtype=np.float64).reshape(-1)
+            if d.size != self.nnz:
+                raise DimensionMismatch(_lib.EDIM, "BlockDiagonal: expected %d values, got %d" % (self.nnz, d.size))
+            self.data = d
+
+    @classmethod
+    def from_blocks(cls, blocks):
+        """From a sequence of equally shaped (mb, nb) arrays."""
+        blocks = [np.asarray(b, dtype=np.float64) for b in blocks]
+        if not blocks or blocks[0].ndim != 2:
+            raise DimensionMismatch(_lib.EDIM, "BlockDiagonal.from_blocks needs a non-empty sequence of matrices")
+        mb, nb = blocks[0].shape
+        for k, b in enumerate(blocks):
+            if b.shape != (mb, nb):
+                raise DimensionMismatch(_lib.EDIM, "BlockDiagonal.from_blocks: block %d is %s, block 0 is %s"
+                                        % (k, b.shape, (mb, nb)))
+        out = cls(len(blocks), mb, nb)
+        for k, b in enumerate(blocks):
+            out.block(k)[:, :] = b
+        return out
+
+    def block(self, b):
+        """Block b as an (mb, nb) VIEW into `.data` (as it is bound at the time of the call)."""
+        if not 0 <= b < self.nblocks:
+            raise IndexError("block %d of %d" % (b, self.nblocks))
+        sz = self.mb * self.nb
+        return self.data[b * sz:(b + 1) * sz].reshape((self.mb, self.nb), order="F")
+
+    def tocsc(self):
+        """The same matrix as scipy.sparse.csc_matrix (canonical order: `.data` of the result equals `.data` here)."""
+        if _sp is None:     # pragma: no cover
+            raise RuntimeError("BlockDiagonal.tocsc needs scipy")
+        m, n = self.shape
+        indptr = np.arange(n + 1, dtype=np.int64) * self.mb
+        rows = (np.arange(self.nblocks, dtype=np.int64)[:, None, None] * self.mb +
+                np.zeros((1, self.nb, 1), dtype=np.int64) + np.arange(self.mb, dtype=np.int64)[None, None, :]).reshape(-1)
+        return _sp.csc_matrix((self.data.copy(), rows.astype(np.int32), indptr.astype(np.int32)), shape=(m, n))
+
+    def toarray(self):
+        out = np.zeros(self.shape)
+        for b in range(self.nblocks):
+            out[b * self.mb:(b + 1) * self.mb, b * self.nb:(b + 1) * self.nb] = self.block(b)
+        return out
+
+
+def _is_blockdiag(J):
+    return isinstance(J, BlockDiagonal)
+
+
 def default_solver(solver, J):
     """types.jl:114-121"""
     matrix_free = type(J).__name__ == "DeviceOperator"
     if solver is None:
-        return LSMR() if (_is_sparse(J) or matrix_free) else QR()
+        return LSMR() if (_is_sparse(J) or _is_blockdiag(J) or matrix_free) else QR()
     if matrix_free and not isinstance(solver, LSMR):
         raise ArgumentError(_lib.EARG, "a matrix-free Jacobian works with LSMR() only (README.md:37-47)")
-    if isinstance(solver, QR) and _is_sparse(J):
+    if isinstance(solver, QR) and (_is_sparse(J) or _is_blockdiag(J)):
         raise ArgumentError(_lib.EARG, "solver QR() is not available for sparse Jacobians. "
                                        "Choose between Cholesky() and LSMR()")
     return solver
@@ -284,7 +353,16 @@ class DeviceMatrix:
         self.ctx = ctx
         h = C.c_void_p()
         L = lib()
-        if _is_sparse(J):
+        self.blockdiag = None
+        if _is_blockdiag(J):
+            self.sparse = True          # (values are addressed like a CSC handle's nzval)
+            self.blockdiag = (J.nblocks, J.mb, J.nb)
+            self.m, self.n = J.shape
+            check(L.lsq_blockdiag_create(ctx.h, J.nblocks, J.mb, J.nb, C.byref(h)))
+            self.h = h
+            self.nnz = J.nnz
+            self.set_values(J.data)
+        elif _is_sparse(J):
             S = J.tocsc()
             S.sort_indices()
             self.sparse = True
@@ -327,6 +405,12 @@ class DeviceMatrix:
         out = np.empty(self.nnz)
         check(lib().lsq_mat_get_values(self.h, out.ctypes.data_as(_lib.c_dp)))
         return out
+
+    def blockdiag_info(self):
+        """lsq_mat_blockdiag_info: (nblocks, mb, nb); (0, 0, 0) for a handle that is not block-diagonal."""
+        a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+        check(lib().lsq_mat_blockdiag_info(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
 
     def set_colscale(self, s):
         """J = V diag(s) (lsq_mat_set_colscale): the values held now are V, `s` a DeviceVector of n factors that stays alive
@@ -570,7 +654,11 @@ class AllocatedSolver:
         check(lib().lsq_solver_chol_path(self.h, C.byref(cpath)))
         panel = C.c_int(0)
         check(lib().lsq_solver_qr_panel(self.h, C.byref(panel)))
-        return dict(lsmr_iter=it.value, lsmr_istop=st.value, qr_rank=rk.value,
+        bpath, bblock = C.c_int(0), C.c_int(-1)
+        check(lib().lsq_solver_blockdiag_path(self.h, C.byref(bpath), C.byref(bblock)))
+        return dict(blockdiag_path={0: None, 1: "batched-unpivoted", 2: "batched-pivoted"}[bpath.value],
+                    blockdiag_block=bblock.value,
+                    lsmr_iter=it.value, lsmr_istop=st.value, qr_rank=rk.value,
                     qr_panel={0: None, 1: "householder-steps", 2: "cholqr2"}[panel.value],
                     qr_path={0: None, 1: "one-stage", 2: "two-stage-pivoted", 3: "two-stage-certified"}[path.value],
                     chol_path={0: None, 1: "one-workgroup", 2: "blocked", 3: "blocked-certified", 4: "blocked-one-launch"}[cpath.value])
@@ -627,6 +715,8 @@ class LeastSquaresProblem:
         if type(J).__name__ == "DeviceOperator":
             if g_ is None:
                 raise ValueError("a matrix-free Jacobian needs g_ (it updates the operator's own state)")
+        elif _is_blockdiag(J):
+            pass              # g_ writes J.data ([block][column][row]) or the views J.block(b)
         elif _is_sparse(J):
             J = J.tocsc()
             J.sort_indices()  # g_ writes J.data in this (canonical CSC) order
@@ -654,7 +744,7 @@ def _central_difference_jacobian(f_, m):
     eps3 = np.finfo(float).eps ** (1.0 / 3.0)
 
     def g_(J, x):
-        if _is_sparse(J):
+        if _is_sparse(J) or _is_blockdiag(J):
             raise ArgumentError(_lib.EARG, "autodiff Jacobians are dense only (types.jl:57)")
         fp, fm = np.zeros(m), np.zeros(m)
         xp = np.array(x, dtype=np.float64)

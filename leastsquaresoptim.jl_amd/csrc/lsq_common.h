@@ -279,6 +279,9 @@ struct lsq_mat {
     // cached colsumabs2 (utils.jl:139-151 is called twice per LM iteration by the reference)
     double *d_colsum = nullptr;
     unsigned long long colsum_version = ~0ull;
+    // block-diagonal Jacobian (lsq_blockdiag_create): a CSC handle that also knows its block shape -- J = blkdiag of
+    // bd_blocks dense bd_mb x bd_nb blocks, nzval = the blocks column-major, back to back.  0 blocks: any other handle
+    int bd_blocks = 0, bd_mb = 0, bd_nb = 0;
 };
 
 // hipMemset runs on the NULL stream and is asynchronous to the host, while the library's stream is

@@ -27,7 +27,8 @@ extern "C" int lsq_solver_create(lsq_ctx *c, lsq_mat *J, int kind, int for_lm, l
         lsq_set_error("solver QR() is not available for sparse Jacobians. Choose between Cholesky() and LSMR()");
         return LSQ_EARG;  // types.jl:115-117
     }
-    if (kind == LSQ_CHOLESKY && J->kind != LSQ_MAT_DENSE) {
+    const bool blockdiag = kind == LSQ_CHOLESKY && J->kind == LSQ_MAT_CSC && J->bd_blocks > 0;   // lsq_blockdiag_create
+    if (kind == LSQ_CHOLESKY && J->kind != LSQ_MAT_DENSE && !blockdiag) {
         lsq_set_error("MethodError: no AbstractAllocatedSolver for Cholesky() with a sparse Jacobian "
                       "(dense_cholesky.jl:19 requires a StridedVecOrMat)");
         return LSQ_EARG;
@@ -39,7 +40,7 @@ extern "C" int lsq_solver_create(lsq_ctx *c, lsq_mat *J, int kind, int for_lm, l
     s->for_lm = for_lm ? 1 : 0;
     s->m = J->m;
     s->n = J->n;
-    int st = (kind == LSQ_LSMR) ? lsq_lsmr_alloc(s) : lsq_dense_solver_alloc(s);
+    int st = (kind == LSQ_LSMR) ? lsq_lsmr_alloc(s) : blockdiag ? lsq_blockdiag_solver_alloc(s, J) : lsq_dense_solver_alloc(s);
     if (st != LSQ_OK) {
         delete s;
         return st;
@@ -83,7 +84,7 @@ extern "C" int lsq_ldiv(lsq_solver *s, lsq_mat *J, const double *y, double *x, i
     }
     switch (s->kind) {
     case LSQ_LSMR: LSQ_TRY(lsq_lsmr_solve(s, J, y, nullptr, x, nmul)); return lsmr_drain(s);
-    case LSQ_CHOLESKY: return lsq_cholesky_solve(s, J, y, nullptr, x, nmul);
+    case LSQ_CHOLESKY: return s->bd_blocks ? lsq_blockdiag_solve(s, J, y, nullptr, x, nmul) : lsq_cholesky_solve(s, J, y, nullptr, x, nmul);
     default: return lsq_qr_solve(s, J, y, nullptr, x, nmul);
     }
 }
@@ -93,7 +94,7 @@ extern "C" int lsq_ldiv_damped(lsq_solver *s, lsq_mat *J, const double *y, doubl
     if (!s || !J || !y || !x || !damp) return LSQ_EARG;
     switch (s->kind) {
     case LSQ_LSMR: LSQ_TRY(lsq_lsmr_solve(s, J, y, damp, x, nmul)); return lsmr_drain(s);
-    case LSQ_CHOLESKY: return lsq_cholesky_solve(s, J, y, damp, x, nmul);
+    case LSQ_CHOLESKY: return s->bd_blocks ? lsq_blockdiag_solve(s, J, y, damp, x, nmul) : lsq_cholesky_solve(s, J, y, damp, x, nmul);
     default: return lsq_qr_solve(s, J, y, damp, x, nmul);
     }
 }

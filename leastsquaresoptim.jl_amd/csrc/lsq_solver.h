@@ -117,6 +117,10 @@ struct lsq_solver {
     bool last_chol_tiles = false;   // the last blocked factorisation was the one-launch one
     bool pub_want = false;          // lsq_tri_chol_solve: let the backward solve's last block publish {info, pipeline flag}
     unsigned long long pub_seq = 0; // ... sequence number of that hand-over (0: it was not launched, use lsq_read_ints)
+    // --- Cholesky() on a block-diagonal Jacobian (lsq_blockdiag.hip): bd_blocks > 0; only d_info is allocated ---
+    int bd_blocks = 0, bd_mb = 0, bd_nb = 0;
+    int last_bd_path = 0;           // lsq_solver_blockdiag_path
+    int last_bd_block = -1;
 };
 int lsq_tri_chol_solve(lsq_solver *s, const double *U, int n, double *d_bx);
 int lsq_tri_chol_fwd_operands(lsq_solver *s, int n, double **z, unsigned long long **slot, unsigned long long *epoch, int **err);
@@ -224,3 +228,6 @@ int lsq_dense_solver_alloc(lsq_solver *s);
 void lsq_dense_solver_free(lsq_solver *s);
 int lsq_cholesky_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);
 int lsq_qr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);
+// implemented in lsq_blockdiag.hip
+int lsq_blockdiag_solver_alloc(lsq_solver *s, const lsq_mat *J);
+int lsq_blockdiag_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);

@@ -32,6 +32,12 @@ def dense_inputs(m, n, seed):
     return v
 
 
+def blockdiag_inputs(nblocks, mb, nb, seed):
+    """Values of blkdiag(A_1 .. A_B) in [block][column][row] order: the dense generator's mb x (B*nb) matrix, column-major --
+    every entry N(0,1)/sqrt(mb), block b = its columns b*nb .. (b+1)*nb - 1."""
+    return dense_inputs(mb, nblocks * nb, seed)
+
+
 def uniform(n, seed, lo=-1.0, hi=1.0):
     v = np.zeros(n)
     check(lib().lsq_synth_uniform(n, seed, lo, hi, v.ctypes.data_as(_lib.c_dp)))
@@ -68,12 +74,27 @@ class _Handle:      # minimal handle wrapper for _run_native
 class TanhProblem:
     """Device-resident problem: Jacobian handle + model (A, b) + x / fcur vectors."""
 
-    def __init__(self, m, n, sparse=True, per_col=None, seed=BASE_SEED, ctx=None, inputs=None, b=None):
+    def __init__(self, m, n, sparse=True, per_col=None, seed=BASE_SEED, ctx=None, inputs=None, b=None, blockdiag=None):
+        """blockdiag=(nblocks, mb, nb): A = blkdiag of nblocks dense mb x nb blocks (m = nblocks*mb, n = nblocks*nb) on a
+        block-diagonal handle (lsq_blockdiag_create); `inputs` / self.A are then the values in [block][column][row] order."""
         self.ctx = ctx or default_context()
         self.m, self.n, self.sparse = m, n, sparse
+        self.blockdiag = None
         L = lib()
         h = C.c_void_p()
-        if sparse:
+        if blockdiag is not None:
+            B, mb, nb = (int(v) for v in blockdiag)
+            if (m, n) != (B * mb, B * nb):
+                raise ValueError("blockdiag=(%d, %d, %d) is a %d x %d problem, not %d x %d" % (B, mb, nb, B * mb, B * nb, m, n))
+            self.blockdiag, self.sparse = (B, mb, nb), True
+            if inputs is None:
+                inputs = blockdiag_inputs(B, mb, nb, seed)
+            self.A = inputs
+            check(L.lsq_blockdiag_create(self.ctx.h, B, mb, nb, C.byref(h)))
+            self.nnz = len(self.A)
+            A3 = self.A.reshape((B, nb, mb))
+            mv = lambda t: np.einsum("bjr,bj->br", A3, t.reshape((B, nb))).reshape(-1)
+        elif sparse:
             if inputs is None:
                 inputs = sparse_inputs(m, n, per_col, seed)
             colptr, rowval, nzval = inputs

@@ -1,0 +1,153 @@
+"""Measurements of Cholesky() on block-diagonal Jacobians (lsq_blockdiag.hip); one JSON line per run.
+
+    python tools/blockdiag_bench.py dense      block solve vs the dense handle's Cholesky() on the stacked matrix
+                                               (B=32, mb=512, nb=64: 16384 x 2048, the C3 shape)
+    python tools/blockdiag_bench.py roofline   solve time vs 8 B mb (nb+1) bytes at 8 TB/s (peak) and 6.3 TB/s (achievable):
+                                               B=8192, mb=256, nb=32 (537 MB of values: past the 256 MiB Infinity Cache) and
+                                               B=65536, mb=64, nb=8
+    python tools/blockdiag_bench.py lm         LM(Cholesky()) on the block handle vs LM(LSMR()) on a plain CSC handle of the
+                                               same matrix (B=8192, mb=256, nb=32): seconds per outer iteration, to convergence
+    python tools/blockdiag_bench.py all
+
+Every solve is timed with HIP events on the library's stream (hipEventRecord through ctypes) around the whole lsq_ldiv_damped
+call -- it ends with the status hand-over to the host, so event time and wall time agree to a few microseconds; both are
+reported.  >= 10 timed repeats after 3 warm-up calls, median and min.  Operands: the library's N(0,1)/sqrt(mb) generator."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import lsq_amd as lsq  # noqa: E402
+
+PEAK_TBS, ACHIEVABLE_TBS = 8.0, 6.3
+
+
+class HipEvents:
+    """hipEvent pairs on the library's stream, through the HIP runtime the library itself is linked against."""
+
+    def __init__(self, ctx):
+        self.hip = C.CDLL("libamdhip64.so")
+        lsq.lib().lsq_ctx_stream.restype = C.c_void_p
+        self.stream = C.c_void_p(lsq.lib().lsq_ctx_stream(ctx.h))
+        self.e0, self.e1 = C.c_void_p(), C.c_void_p()
+        for e in (self.e0, self.e1):
+            assert self.hip.hipEventCreate(C.byref(e)) == 0
+
+    def start(self):
+        assert self.hip.hipEventRecord(self.e0, self.stream) == 0
+
+    def stop(self):
+        assert self.hip.hipEventRecord(self.e1, self.stream) == 0
+        assert self.hip.hipEventSynchronize(self.e1) == 0
+        ms = C.c_float(0.0)
+        assert self.hip.hipEventElapsedTime(C.byref(ms), self.e0, self.e1) == 0
+        return ms.value * 1e-3
+
+
+def time_solve(ctx, sv, dx, dy, dd, reps, warmup=3):
+    evs = HipEvents(ctx)
+    ev, wall = [], []
+    for k in range(warmup + reps):
+        ctx.sync()
+        t0 = time.perf_counter()
+        evs.start()
+        sv.ldiv_(dx, dy, dd)
+        sec = evs.stop()
+        t1 = time.perf_counter()
+        if k >= warmup:
+            ev.append(sec)
+            wall.append(t1 - t0)
+    return {"event_median_s": statistics.median(ev), "event_min_s": min(ev), "wall_median_s": statistics.median(wall),
+            "wall_min_s": min(wall), "reps": reps}
+
+
+def block_operands(ctx, B, mb, nb, seed):
+    J = lsq.BlockDiagonal(B, mb, nb, data=lsq.synthetic.blockdiag_inputs(B, mb, nb, seed))
+    rng = np.random.default_rng(seed)
+    y = rng.standard_normal(B * mb)
+    damp = 0.05 + rng.random(B * nb)
+    return J, y, damp
+
+
+def bench_dense(ctx, reps):
+    B, mb, nb = 32, 512, 64
+    J, y, damp = block_operands(ctx, B, mb, nb, 1)
+    out = {"bench": "block_vs_dense", "B": B, "mb": mb, "nb": nb}
+    xs = {}
+    for name, host in (("block", J), ("dense", J.toarray())):
+        Jd = lsq.DeviceMatrix(ctx, host)
+        sv = lsq.AllocatedSolver(Jd, lsq.Cholesky(), for_lm=True)
+        dx, dy, dd = lsq.DeviceVector(ctx, Jd.n), lsq.DeviceVector(ctx, Jd.m, y), lsq.DeviceVector(ctx, Jd.n, damp)
+        out[name] = time_solve(ctx, sv, dx, dy, dd, reps)
+        out[name]["path"] = sv.info()["blockdiag_path"] or sv.info()["chol_path"]
+        xs[name] = dx.get()
+    out["rel_diff"] = float(np.linalg.norm(xs["block"] - xs["dense"]) / np.linalg.norm(xs["dense"]))
+    out["speedup_event_median"] = out["dense"]["event_median_s"] / out["block"]["event_median_s"]
+    print(json.dumps(out))
+
+
+def bench_roofline(ctx, reps):
+    for B, mb, nb in ((8192, 256, 32), (65536, 64, 8)):
+        J, y, damp = block_operands(ctx, B, mb, nb, 2)
+        Jd = lsq.DeviceMatrix(ctx, J)
+        sv = lsq.AllocatedSolver(Jd, lsq.Cholesky(), for_lm=True)
+        dx, dy, dd = lsq.DeviceVector(ctx, Jd.n), lsq.DeviceVector(ctx, Jd.m, y), lsq.DeviceVector(ctx, Jd.n, damp)
+        t = time_solve(ctx, sv, dx, dy, dd, reps)
+        nbytes = 8.0 * B * mb * (nb + 1) + 16.0 * B * nb
+        out = {"bench": "roofline", "B": B, "mb": mb, "nb": nb, "bytes": nbytes, **t}
+        out["tb_per_s_event_median"] = nbytes / t["event_median_s"] * 1e-12
+        out["fraction_of_peak_8TBs"] = out["tb_per_s_event_median"] / PEAK_TBS
+        out["fraction_of_achievable_6.3TBs"] = out["tb_per_s_event_median"] / ACHIEVABLE_TBS
+        print(json.dumps(out))
+        Jd.free()
+
+
+def bench_lm(ctx, reps):
+    B, mb, nb = 8192, 256, 32
+    m, n = B * mb, B * nb
+    out = {"bench": "lm_cholesky_vs_lsmr", "B": B, "mb": mb, "nb": nb}
+    pr = lsq.synthetic.TanhProblem(m, n, seed=4, ctx=ctx, blockdiag=(B, mb, nb))
+    A, b = pr.A, pr.b
+    S = lsq.BlockDiagonal(B, mb, nb, data=A).tocsc()
+    pl = lsq.synthetic.TanhProblem(m, n, sparse=True, seed=4, ctx=ctx, b=b,
+                                   inputs=(S.indptr.astype(np.int32), S.indices.astype(np.int32), A))
+    for name, p, kind in (("cholesky_block", pr, lsq._lib.CHOLESKY), ("lsmr_csc", pl, lsq._lib.LSMR)):
+        runs = []
+        for k in range(2 + reps):
+            p.reset()
+            r = p.optimize(lsq._lib.LEVENBERG_MARQUARDT, kind, iterations=50, fetch_x=False)
+            if k >= 2:
+                runs.append(r)
+        sec = [r.seconds for r in runs]
+        r = runs[-1]
+        out[name] = {"converged": r.converged, "outer_iterations": r.iterations, "lsmr_inner_iterations": r.lsmr_iterations,
+                     "ssr": r.ssr, "seconds_median": statistics.median(sec), "seconds_min": min(sec),
+                     "seconds_per_outer_median": statistics.median(sec) / max(r.iterations, 1), "reps": reps}
+    out["speedup_to_convergence"] = out["lsmr_csc"]["seconds_median"] / out["cholesky_block"]["seconds_median"]
+    print(json.dumps(out))
+    pr.close()
+    pl.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("what", choices=["dense", "roofline", "lm", "all"])
+    ap.add_argument("--reps", type=int, default=20)
+    a = ap.parse_args()
+    ctx = lsq.default_context()
+    if a.what in ("dense", "all"):
+        bench_dense(ctx, max(a.reps, 10))
+    if a.what in ("roofline", "all"):
+        bench_roofline(ctx, max(a.reps, 10))
+    if a.what in ("lm", "all"):
+        bench_lm(ctx, max(a.reps, 10))
+
+
+if __name__ == "__main__":
+    main()
