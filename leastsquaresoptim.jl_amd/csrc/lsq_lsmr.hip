@@ -11,7 +11,7 @@
 // (iterative_lsmr.jl:12-122) become epilogue arithmetic; u is kept UNNORMALISED (its 1/beta is
 // folded into the consumer), which removes the rmul! passes over the m-vector (lsmr.jl:121).
 // The recurrence lives in device memory; the host learns about termination through a pinned
-// mailbox word and runs at most LSQ_LOOKAHEAD iterations ahead (kernels of a finished solve exit
+// mailbox word and runs at most LSQ_LOOKAHEAD_DEFAULT iterations ahead (kernels of a finished solve exit
 // on their first instruction).  Stopping rules are evaluated every iteration, so `iter` (and
 // mul_calls = 2*iter, lsmr.jl:236) is the count the reference would report.
 #include <chrono>
@@ -22,7 +22,6 @@
 #include "lsq_spmv.h"
 
 static constexpr int LSQ_LOOKAHEAD_DEFAULT = 2;
-static constexpr bool LSQ_TAIL_REACT_DEFAULT = true;       // (lsq_lsmr_solve, three-launch iteration: react to a cautious launch instead of pre-placing the tail)
 
 // mailbox word: [63:41] epoch | [40] done | [39:32] istop | [31:0] iter
 __device__ __forceinline__ void publish(LsqMailbox *mail, const LsmrState *st) {
@@ -619,6 +618,413 @@ bool lsq_lsmr_takes_lm_prep(const lsq_solver *s, const lsq_mat *J) {
            !getenv("LSQ_LSMR_SEPARATE_SETUP");
 }
 
+// ---- the host side of a solve: what the two loops below share -----------------------------------------------------------------
+// the progress word as the host reads it (layout: publish)
+struct LsmrProgress {
+    bool ours, done;     // written by THIS solve (its epoch) / that solve is over
+    int istop, iter;
+    LsmrProgress(unsigned long long w, unsigned epoch)
+        : ours((unsigned)(w >> 41) == epoch), done(((w >> 40) & 1ull) != 0), istop((int)((w >> 32) & 0xff)), iter((int)(w & 0xffffffffu)) {}
+};
+static inline unsigned long long lsmr_progress_word(const lsq_ctx *c) { return *(volatile unsigned long long *)c->h_mail; }
+
+// Where the solve will stop, predicted from the hints the device publishes beside the progress word: test1 = |r|/|b| and
+// test2 = |A'r|/(|A||r|).  A solve is over when test1 <= btol (+ a 1e-6-sized term) or test2 <= atol (lsmr.jl:224-231; the other
+// rules do not fire on these operators), and on the damped, Jacobi-preconditioned operators of an LM run test2 falls
+// geometrically (C4: x 0.07-0.09 per iteration, every iteration).
+struct StopPredictor {
+    double t1_prev, t2_prev, ratio2;   // (-1: none yet); ratio2 = test2(k) / test2(k-1), at first the previous solve's (lsq_solver::lsmr_ratio2)
+    int hint_it;                       // last iteration whose hints went into the prediction
+    // `w`: the progress word that announced iteration `it`.  Returns the planned last iteration, or 0 (nothing new to say).
+    int update(const LsqMailbox *mail, unsigned long long w, int it, double atol, double btol) {
+        if (!(it > hint_it && it >= 1)) return 0;
+        const double h1 = mail->test1, h2 = mail->test2;
+        const unsigned long long w2 = *(volatile unsigned long long *)mail;
+        if (!(w2 == w && h1 > 0.0 && h2 > 0.0)) return 0;   // (the pair belongs to iteration `it` only if the word did not move meanwhile)
+        if (t2_prev > 0.0 && h2 < t2_prev) ratio2 = std::min(0.95, std::max(1e-4, h2 / t2_prev));
+        int k = 1 << 20;
+        if (h2 > atol && ratio2 < 1.0) k = std::min(k, (int)std::ceil(std::log(atol / h2) / std::log(ratio2) - 1e-9));
+        if (t1_prev > 0.0 && h1 < 0.98 * t1_prev && h1 > btol)       // test1 still falling: when does it reach btol?
+            k = std::min(k, (int)std::ceil(std::log(btol / h1) / std::log(h1 / t1_prev) - 1e-9));
+        t1_prev = h1; t2_prev = h2; hint_it = it;
+        return k < (1 << 20) ? it + std::max(1, k) : 0;
+    }
+};
+
+struct LsmrRun {     // what a loop knows about its solve
+    int it = 0, istop = 0;
+    bool finished = false;
+    bool tail_ran = false;      // a guarded tail, queued inside the loop, is known to have run
+    bool see(const LsmrProgress &p) {     // true: the solve is over
+        if (p.ours) it = p.iter;
+        if (p.ours && p.done) { istop = p.istop; finished = true; }
+        return finished;
+    }
+};
+
+// The waiting host's fallback (every 1024th idle poll).  A failed stream will never move the mailbox: error.  A drained stream
+// whose progress word is neither final nor at `committed` (the iteration the newest enqueued launch commits) means the mailbox
+// is not visible (should not happen with coherent host memory): read the state `d_st` instead.  `spent`: the iteration budget
+// is used up, i.e. nothing more will be enqueued.
+static int lsmr_stream_drained(lsq_ctx *c, unsigned epoch, int committed, const LsmrState *d_st, bool spent, LsmrRun &r) {
+    const hipError_t sq = hipStreamQuery(c->stream);
+    if (sq != hipSuccess && sq != hipErrorNotReady) {   // launch failure / device fault
+        lsq_set_error("HIP error inside the LSMR iteration: %s", hipGetErrorString(sq));
+        return LSQ_EHIP;
+    }
+    if (sq != hipSuccess) return LSQ_OK;
+    // stream drained: whatever the mailbox shows now is final for the enqueued work
+    const LsmrProgress p(lsmr_progress_word(c), epoch);
+    if (p.ours && (p.done || p.iter >= committed)) return LSQ_OK;    // (the loop reads it next)
+    LsmrState hs;
+    LSQ_HIP(hipMemcpy(&hs, d_st, sizeof(hs), hipMemcpyDeviceToHost));
+    r.it = hs.iter;
+    if (hs.done) {
+        r.istop = hs.istop;
+        r.finished = true;
+    } else if (spent) {
+        lsq_set_error("lsmr: iteration budget exhausted without a stop rule");
+        return LSQ_EHIP;
+    }
+    return LSQ_OK;
+}
+
+// instrumentation: launches queued beyond the stopping iteration returned on their first instruction (the K1' that committed the
+// stop skipped its product) -- drop their samples so the reported average is over working launches only
+struct LsmrProf {
+    size_t base[2];                // samples per kernel id that were there before this solve
+    std::vector<int> iter[2];      // iteration number (1-based) of every timed launch of this solve
+};
+static void lsmr_drop_idle_samples(lsq_ctx *c, LsmrProf &p, int it) {
+    for (int k = 0; k < 2; ++k) {
+        auto &v = c->prof_ev[k];
+        while (v.size() > p.base[k] && !p.iter[k].empty() && p.iter[k].back() > it) {
+            hipEventDestroy(v.back()); v.pop_back();
+            hipEventDestroy(v.back()); v.pop_back();
+            p.iter[k].pop_back();
+        }
+    }
+}
+
+// One solve's operands, constants and its view of the solver's buffers, built once by lsq_lsmr_solve
+struct LsmrWork {
+    lsq_solver *s;
+    lsq_ctx *c;
+    lsq_mat *J;
+    const double *d_y;
+    double *d_x;
+    int m, n;
+    bool damped, sharded;
+    bool fused;                    // the three-launch iteration (lsq_lsmr3.h); else K1 | K2 | K3
+    double atol, btol, conlim;
+    int maxiter, lookahead;
+    unsigned epoch;
+    int gn;                        // grid of the n-vector kernels
+    const double *dgk;             // sqrt(damp), or null
+    const LsmrTail *tail;          // the caller's (may be null)
+    bool dynamic, spec;            // the stop is predicted from the solve's own hints / the tail's place depends on a guess at all
+    LsmrState *stb[2];             // the three-launch iteration double-buffers the state; the four-launch one lives in [0]
+    double *pu, *pv;               // deferred-reduction partials (sum u~^2 / sum v~^2); fused: pu is fpu[0]
+    int *npu, *npv;
+    double *pxb[2];                // sum(u~x^2) partials, double-buffered: K3 reads iteration k's while writing k+1's
+    int *npxb[2];
+    double *vset;                  // where the setup (and every K2) leaves v~
+    // the three-launch iteration's second copies (lsq_lsmr_alloc: d_f3)
+    double *fx[2], *fhbar[2], *fh[2];
+    double *fw;                    // gather vector of the next J*v: (v~ .* P) .* s
+    double *fpu[2];
+    int *fnpu;                     // two counts
+    LsmrHandoff *fho;              // the in-launch record of k_lsmr_fused
+};
+
+// K2's epilogue on the four-launch loop's buffers, as the setup uses it (no u~x, no px yet)
+static EpiV lsmr_epi_v(const LsmrWork &W) {
+    return EpiV{&W.stb[0]->done, 0, W.stb[0], W.pu, W.npu, nullptr, nullptr, W.s->d_P, W.dgk, nullptr, W.s->d_v, W.pv, W.npv,
+                nullptr, 0.0, 0.0, 0, 0};
+}
+// K3 of the four-launch loop.  px_in: the partials of this iteration's sum(u~x^2) (null in the setup: u~x is still zero, so only
+// sum(u~_y^2) enters beta_1), `out`: the px buffer that receives the next iteration's.  `summed`: sum(u~_y^2) is the ranks' sum
+// that rowshard_adjoint left behind the all-reduced vector, not this rank's partials
+static void lsmr_launch_update(const LsmrWork &W, bool summed, const double *px_in, const int *npx_in, int out) {
+    lsq_solver *s = W.s; lsq_ctx *c = W.c;
+    LSQ_LAUNCH(k_lsmr_update, dim3(W.gn), dim3(LSQ_NT), 0, c->stream, W.n, W.stb[0], c->d_mail,
+                       summed ? (const double *)(s->d_xbuf + W.n) : (const double *)W.pu,
+                       summed ? (const int *)s->d_one : (const int *)W.npu, W.pv, W.npv, px_in, npx_in, W.pxb[out], W.npxb[out],
+                       W.dgk, s->d_ux, s->d_P, s->d_v, s->d_h, s->d_hbar, s->d_rhs, W.d_x, s->d_t, c->d_partials, lsq_ctr(c, 3));
+}
+
+// P, sqrt(damp), the state reset and v~ = P.*(A'b)/beta_1; the four-launch loop's K3 in "first" mode behind it (the three-launch
+// iteration's first K1' does that itself)
+static int lsmr_enqueue_setup(const LsmrWork &W, double *d_damp, const double *d_Jty, double y_sumsq, const LsmrLmPrep *lm,
+                              const double *colsum, int custom_p) {
+    lsq_solver *s = W.s; lsq_ctx *c = W.c; lsq_mat *J = W.J;
+    const int m = W.m, n = W.n;
+    LsmrState *st = W.stb[0];
+    const double *cscale = W.fused ? J->d_colscale : nullptr;
+    double *wout = W.fused ? W.fw : nullptr;
+    bool summed = false;           // (a caller's J'y comes with sum(y^2) of ALL rows, or with every rank's own k_lsmr_begin)
+    auto launch_begin = [&]() {
+        long long gb = std::min<long long>(lsq_div_up(m > 0 ? m : 1, LSQ_NT), (long long)c->num_cus * 8);
+        if (gb > 4096) gb = 4096;
+        LSQ_LAUNCH(k_lsmr_begin, dim3((int)gb), dim3(LSQ_NT), 0, c->stream, m, W.d_y, st, W.pu, W.npu, W.atol,
+                           W.btol, 1.0 / W.conlim, W.maxiter, W.epoch);
+    };
+    if (lm) {
+        if (!(d_Jty && y_sumsq >= 0.0 && W.damped && lsq_lsmr_takes_lm_prep(s, J))) {
+            lsq_set_error("lsmr: LM preparation requested where it does not apply");
+            return LSQ_EARG;
+        }
+        LSQ_LAUNCH(k_lm_lsmr_setup, dim3(lsq_div_up(n, 1024)), dim3(1024), 0, c->stream, n, *lm, d_damp, s->d_P, s->d_dg,
+                           s->d_ux, d_Jty, W.vset, st, W.pu, W.npu, y_sumsq, W.pv, W.npv, W.atol, W.btol, 1.0 / W.conlim, W.maxiter,
+                           W.epoch, cscale, wout);
+    } else if (d_Jty) {
+        if (!(y_sumsq >= 0.0)) launch_begin();
+        LSQ_LAUNCH(k_lsmr_setup, dim3(W.gn), dim3(LSQ_NT), 0, c->stream, n, colsum, d_damp, s->d_P, s->d_dg,
+                           s->d_ux, d_Jty, W.vset, st, W.pu, W.npu, y_sumsq >= 0.0 ? y_sumsq : -1.0, W.pv, W.npv, W.atol, W.btol,
+                           1.0 / W.conlim, W.maxiter, W.epoch, custom_p, cscale, wout);
+    } else {
+        LSQ_LAUNCH(k_lsmr_prep, dim3(W.gn), dim3(LSQ_NT), 0, c->stream, n, colsum, d_damp, s->d_P,
+                           s->d_dg, s->d_ux, custom_p);
+        launch_begin();
+        LSQ_HIP(hipGetLastError());
+        // v~ = A'u (setup)
+        EpiV ev = lsmr_epi_v(W);
+        if (W.fused) { ev.vout = W.vset; ev.cs = J->d_colscale; ev.wout = W.fw; }
+        if (W.sharded) LSQ_TRY(rowshard_adjoint(s, J, W.d_y, ev, W.pu, W.npu));
+        else LSQ_TRY(launch_product(J, 1, W.d_y, ev));
+        summed = W.sharded;
+    }
+    if (!W.fused) lsmr_launch_update(W, summed, nullptr, nullptr, 0);     // it already forms iteration 1's u~x
+    LSQ_HIP(hipGetLastError());
+    return LSQ_OK;
+}
+
+// ---- three launches per inner iteration: K1' (k_lsmr_fused: decides iteration j-1, updates the n-vectors, J*v of iteration j) |
+// K2a (k_sell_cols) | K2b (k_combine<EpiV>).  Launch j of K1' reads state / partials / x, hbar, h number (j-1)&1 and writes number
+// j&1; it reports iteration j-1 in the progress word.
+// The caller's tail: the host REACTS, it does not pre-place (round 6; profiles/r06/ab_tail_react.txt).  A guarded tail queued
+// behind the launch that is expected to commit the stop costs nothing when the guess holds, but ~50 us when it does not: five
+// launches of full grids that skip themselves stand between the solve's next product and the queue's head (measured: perfect
+// first guesses would gain 3.6 % on C4).  Here the expected stop only makes that launch CAUTIOUS, and nothing more is queued
+// until it has reported (~8 us into it): if the solve is over the caller (lsq_lsmr_solve) queues the tail, unguarded, while the
+// cautious launch winds down; if not, the product of that launch is still streaming for 20 us and the next launches are queued
+// behind it as usual.  A wrong guess then costs a late product.
+static int lsmr_run_fused(const LsmrWork &W, StopPredictor &pred, LsmrRun &r) {
+    lsq_solver *s = W.s; lsq_ctx *c = W.c; lsq_mat *J = W.J;
+    const LsmrTail *tail = W.tail;
+    const int m = W.m, n = W.n;
+    int planned = W.spec ? tail->predict : 0;      // the iteration expected to be the last: the caller's guess, then the solve's own
+    int wait_at = 0;             // the iteration whose commit (by a cautious launch) is awaited before anything else is queued
+    bool wait_is_guess = false;  //   ... and that launch was cautious because of a PREDICTION (counted), not only because nothing was known
+    const LsqSell &S = J->srows;
+    const int nxpad = (n + 1) & ~1;
+    const size_t lds = (size_t)(nxpad + LSQ_SELL_ROWS_MAX) * sizeof(double);
+    LSQ_TRY(lsq_set_lds(c, (const void *)k_lsmr_fused<0>, (LSQ_LDS_X_MAX + LSQ_SELL_ROWS_MAX) * sizeof(double)));
+    // update workgroups: the CUs the sliced rows leave without a block (C4: 253 blocks on 256 CUs -> 3), at least 3
+    int ub = c->num_cus - S.nblocks;
+    ub = ub < 3 ? 3 : (ub > LSQ_FUSED_UB_MAX ? LSQ_FUSED_UB_MAX : ub);
+    const int pb = std::max(1, std::min(S.nblocks, c->num_cus - ub));
+    int k1 = 0, enq = 0;         // K1' launches / whole iterations enqueued: k1 is enq or enq + 1
+    const int test_no_record = getenv("LSQ_TEST_EXCHANGE_TIMEOUT") ? 1 : 0;       // (read once per solve, not per launch)
+    LsmrProf prof{{c->prof_ev[0].size(), c->prof_ev[1].size()}, {}};
+    unsigned long long spins = 0;
+    // cautious: the product workgroups wait for the decision before they stream
+    auto launch_k1 = [&](bool cautious) -> int {
+        const int j = k1 + 1, in = (j - 1) & 1, out = j & 1;
+        LsmrFused a;
+        a.st_in = W.stb[in]; a.st_out = W.stb[out]; a.mail = c->d_mail;
+        a.pu_in = W.fpu[in]; a.npu_in = W.fnpu + in; a.pu_out = W.fpu[out]; a.npu_out = W.fnpu + out;
+        a.px_in = (W.damped && j > 1) ? W.pxb[in] : nullptr; a.npx_in = W.npxb[in];
+        a.px_out = W.pxb[out]; a.npx_out = W.npxb[out];
+        a.pv = W.pv; a.npv = W.npv;
+        a.vt = W.vset; a.w = W.fw; a.P = s->d_P; a.dg = W.dgk;
+        a.h_in = W.fh[in]; a.hbar_in = W.fhbar[in]; a.x_in = W.fx[in];
+        a.h_out = W.fh[out]; a.hbar_out = W.fhbar[out]; a.x_out = W.fx[out];
+        a.v = s->d_v; a.xout = W.d_x; a.ux = s->d_ux;
+        a.uold = j == 1 ? W.d_y : s->d_u; a.unew = s->d_u;
+        a.n = n; a.ub = ub;
+        a.cautious = cautious ? 1 : 0;
+        a.test_no_record = test_no_record;                      // (test hook: the in-launch hand-off fails)
+        a.ho = W.fho;
+        a.tag_prev = j > 1 ? s->f3_tag : 0u;
+        if (++s->f3_tag == 0u) s->f3_tag = 1u;                  // a counter per solver (= per record buffer): every older record
+        a.tag = s->f3_tag;                                      // carries another value; 0 is the zeroed buffer
+        if (c->prof_kernels & 1) lsq_prof_mark(c, 0, 0);
+        hipEvent_t e0, e1;
+        if (lsq_prof_take(c, &e0, &e1)) {
+            LSQ_LAUNCH_TIMED(k_lsmr_fused<0>, dim3(pb + ub), dim3(LSQ_BIG_NT), lds, c->stream, e0, e1, 0, sell_dev(S), S.wrows, m, nxpad, a);
+            prof.iter[0].push_back(j);
+        } else {
+            LSQ_LAUNCH(k_lsmr_fused<0>, dim3(pb + ub), dim3(LSQ_BIG_NT), lds, c->stream, sell_dev(S), S.wrows, m, nxpad, a);
+        }
+        if (c->prof_kernels & 1) lsq_prof_mark(c, 0, 1);
+        LSQ_HIP(hipGetLastError());
+        ++k1;
+        return LSQ_OK;
+    };
+    auto launch_k2 = [&]() -> int {      // K2 of iteration enq + 1 (its K1' is launch k1 == enq + 1)
+        const int j = enq + 1, cur = j & 1;
+        LsmrState *st = W.stb[cur];
+        EpiV e2{&st->done, 0, st, W.fpu[cur], W.fnpu + cur, W.damped ? W.pxb[cur] : nullptr, W.npxb[cur], s->d_P, W.dgk,
+                W.damped ? s->d_ux : nullptr, s->d_v, W.pv, W.npv, nullptr, 0.0, 0.0, 0, 0};
+        e2.vout = W.vset; e2.cs = J->d_colscale; e2.wout = W.fw;
+        if (c->prof_kernels & 2) lsq_prof_mark(c, 1, 0);
+        const size_t before = c->prof_ev[1].size();
+        LSQ_TRY(launch_sell_cols<false>(J, s->d_u, &st->done));
+        if (c->prof_ev[1].size() > before) prof.iter[1].push_back(j);
+        if (c->prof_kernels & 2) lsq_prof_mark(c, 1, 1);
+        const int nb = lsq_div_up(n, LSQ_CMB_COLS);
+        LSQ_LAUNCH((k_combine<EpiV>), dim3(std::min(nb, 2048)), dim3(LSQ_NT), 0, c->stream, J->scols.d_part, n, J->scols.ngw, e2, nb,
+                   J->d_colscale);
+        LSQ_HIP(hipGetLastError());
+        ++enq;
+        return LSQ_OK;
+    };
+    while (!r.finished) {
+        const unsigned long long w = lsmr_progress_word(c);
+        const LsmrProgress p(w, W.epoch);
+        if (r.see(p)) break;
+        if (wait_at > 0 && p.ours && r.it >= wait_at) {           // the cautious launch found the solve unfinished
+            if (wait_is_guess) {
+                c->tail_spec[0]++;
+                c->tail_spec[1]++;
+                planned = 0;
+            }
+            wait_at = 0;
+        }
+        if (W.dynamic && p.ours) {
+            const int stop = pred.update(c->h_mail, w, r.it, W.atol, W.btol);
+            if (stop > 0) planned = stop;
+        }
+        if (!(wait_at > 0 && r.it < wait_at)) {               // (else: a cautious launch is deciding iteration wait_at)
+            if (k1 == enq + 1) {                                 // the rest of iteration enq + 1
+                LSQ_TRY(launch_k2());
+                spins = 0;
+                continue;
+            }
+            // K1' number enq + 1 commits iteration enq: it does not count against the look-ahead (nothing is decided without it)
+            if (enq - r.it < W.lookahead + 1 && enq < W.maxiter + 1) {
+                // cautious: the launch that commits the planned last iteration (or the newest one, if the prediction names an
+                // iteration whose commit is already in the queue) ...
+                const bool guess = W.spec && planned > 0 && enq >= planned && enq >= 1;
+                // ... and also where nothing is known yet: the launch that decides iteration 1, unless the previous solve was a
+                // long one
+                const bool unknown = W.spec && enq == 1 && pred.hint_it == 0 && tail->predict <= 3;
+                LSQ_TRY(launch_k1(guess || unknown));
+                if (guess || unknown) {                          // nothing behind it until it has decided
+                    wait_at = enq;
+                    wait_is_guess = guess;
+                }
+                spins = 0;
+                continue;
+            }
+        }
+        if (c->idle_hook) lsq_run_idle_hook(c);
+        if ((++spins & 0x3ffu) != 0) continue;
+        LSQ_TRY(lsmr_stream_drained(c, W.epoch, k1 - 1, W.stb[k1 & 1], enq >= W.maxiter + 1, r));
+    }
+    lsmr_drop_idle_samples(c, prof, r.it);
+    if (r.istop == 99) {     // (a product workgroup gave up waiting for workgroup 0's record: lsq_lsmr3.h)
+        lsq_set_error("lsmr: the in-launch hand-off of k_lsmr_fused timed out");
+        return LSQ_EHIP;
+    }
+    // a stop BEFORE wait_at (it < wait_at: an older launch committed it) is counted as a right guess here; to be fixed
+    if (wait_at > 0 && wait_is_guess) c->tail_spec[0]++;          // the predicted stop was the stop (a right guess)
+    return LSQ_OK;
+}
+
+// ---- four launches per inner iteration: K1 (J*v, EpiU) | K2 (J'u: k_sell_cols + k_combine<EpiV>, or the row-sharded form with
+// the ranks' sum in the middle) | K3 (k_lsmr_update).  Row-sharded solves, wide n, unsliced layouts, LSQ_LSMR_FOUR_LAUNCHES=1.
+// The caller's tail is PRE-PLACED (LsmrTail, lsq_solver.h): queued, guarded by the state's `notdone`, right behind the iteration
+// that is planned to be the last -- first the caller's guess (the previous solve's count), from iteration 1 on the solve's own
+// prediction (StopPredictor).
+static int lsmr_run_four(const LsmrWork &W, StopPredictor &pred, LsmrRun &r) {
+    lsq_solver *s = W.s; lsq_ctx *c = W.c; lsq_mat *J = W.J;
+    const LsmrTail *tail = W.tail;
+    const bool sharded = W.sharded;
+    const int maxiter = W.maxiter;
+    LsmrState *st = W.stb[0];
+    EpiU eu{&st->done, 0, st, W.d_y, s->d_u, W.n, s->d_dg, s->d_t, s->d_ux, W.pu, W.npu, nullptr, 0.0};
+    EpiV ev = lsmr_epi_v(W);
+    ev.ux = W.damped ? s->d_ux : nullptr;
+    int planned = W.spec ? tail->predict : 0;
+    int tail_at = 0;             // iteration behind which the latest guarded tail was enqueued (0: none that is still undecided)
+    int enq = 0;                 // whole iterations enqueued
+    LsmrProf prof{{c->prof_ev[0].size(), c->prof_ev[1].size()}, {}};
+    unsigned long long spins = 0;
+    while (!r.finished) {
+        const unsigned long long w = lsmr_progress_word(c);
+        const LsmrProgress p(w, W.epoch);
+        if (r.see(p)) break;
+        if (W.spec && p.ours && tail_at > 0 && r.it >= tail_at) {   // (not done: `finished` left the loop above)
+            // the tail behind iteration tail_at found the solve unfinished and skipped itself: a wrong guess
+            c->tail_spec[0]++;
+            c->tail_spec[1]++;
+            tail_at = 0;
+            planned = 0;
+        }
+        if (W.dynamic && p.ours) {
+            const int stop = pred.update(c->h_mail, w, r.it, W.atol, W.btol);
+            if (stop > 0 && tail_at == 0) planned = stop;
+        }
+        // the guarded tail: right behind the planned last iteration, as soon as that one is enqueued (or behind the newest
+        // enqueued, still unreported one if the prediction names an iteration that is already in the queue)
+        if (W.spec && tail_at == 0 && planned > 0 && enq >= planned && enq > r.it) {
+            LSQ_TRY(tail->fn(&st->notdone, tail->user));
+            tail_at = enq;
+        }
+        // Row-sharded: every rank must enqueue the SAME number of inner iterations (each carries a collective), so the count
+        // cannot depend on when this host happens to see the mailbox: iterations go out in chunks of `lookahead`, and the
+        // next chunk only once the last one has reported "not done" -- ceil(stop / lookahead) * lookahead on every rank.
+        // (and the first chunk only once the SETUP has reported: a solve that is over before it starts -- A'b = 0 -- must not
+        //  get a chunk on the ranks whose host looked too early)
+        // (a speculative tail sits behind iteration tail_at: nothing more is queued until that iteration has reported)
+        const bool hold = tail_at > 0 && enq == tail_at && r.it < tail_at;
+        const bool want = sharded ? (p.ours && enq == r.it && enq < maxiter) : (!hold && enq - r.it < W.lookahead && enq < maxiter);
+        if (want) {
+            const int chunk = sharded ? (int)std::min<long long>(W.lookahead, (long long)maxiter - enq) : 1;
+            for (int q = 0; q < chunk; ++q) {
+                if (c->prof_kernels & 1) lsq_prof_mark(c, 0, 0);
+                {
+                    const size_t before = c->prof_ev[0].size();
+                    LSQ_TRY(launch_product(J, 0, s->d_t, eu));   // K1
+                    if (c->prof_ev[0].size() > before) prof.iter[0].push_back(enq + 1);
+                }
+                if (c->prof_kernels & 1) lsq_prof_mark(c, 0, 1);
+                eu.uold = s->d_u;                            // after the first iteration u~ lives in d_u
+                const int cur = enq & 1;                     // px buffer holding this iteration's sum(u~x^2)
+                ev.px = W.damped ? W.pxb[cur] : nullptr;
+                ev.npx = W.npxb[cur];
+                if (c->prof_kernels & 2) lsq_prof_mark(c, 1, 0);
+                {
+                    const size_t before = c->prof_ev[1].size();
+                    if (sharded) LSQ_TRY(rowshard_adjoint(s, J, s->d_u, ev, W.pu, W.npu));   // K2 with the ranks' sum in the middle
+                    else LSQ_TRY(launch_product(J, 1, s->d_u, ev));   // K2
+                    if (c->prof_ev[1].size() > before) prof.iter[1].push_back(enq + 1);
+                }
+                if (c->prof_kernels & 2) lsq_prof_mark(c, 1, 1);
+                lsmr_launch_update(W, sharded, ev.px, ev.npx, cur ^ 1);   // K3
+                LSQ_HIP(hipGetLastError());
+                ++enq;
+            }
+            spins = 0;
+            continue;
+        }
+        if (c->idle_hook) lsq_run_idle_hook(c);   // look-ahead window full: the device has work for a while
+        if ((++spins & 0x3ffu) != 0) continue;
+        LSQ_TRY(lsmr_stream_drained(c, W.epoch, enq, st, enq >= maxiter, r));
+    }
+    lsmr_drop_idle_samples(c, prof, r.it);
+    // the latest guarded tail ran iff the solve was over when its kernels reached the device: stop iteration <= tail_at
+    // (tails that skipped themselves were counted, as wrong guesses, when their iteration reported)
+    if (tail_at > 0) {
+        c->tail_spec[0]++;
+        if (r.it > tail_at) c->tail_spec[1]++;
+        else r.tail_ran = true;
+    }
+    return LSQ_OK;
+}
+
 int lsq_lsmr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, double *d_damp, double *d_x, int *nmul,
                    const double *d_Jty, double y_sumsq, const LsmrLmPrep *lm, const LsmrTail *tail) {
     lsq_ctx *c = s->ctx;
@@ -640,39 +1046,36 @@ int lsq_lsmr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, double *d_damp,
         LSQ_TRY(lsq_lsmr_exact_solve(s, J, d_y, d_damp, d_x, nmul));
         return tail && tail->fn ? tail->fn(nullptr, tail->user) : LSQ_OK;
     }
-    static const int lookahead_env = [] {
-        const char *e = getenv("LSQ_LOOKAHEAD");
-        int v = e ? atoi(e) : LSQ_LOOKAHEAD_DEFAULT;
-        return v < 1 ? 1 : v;
-    }();
-    const int lookahead = lsq_dbg_serial ? 1 : lookahead_env;   // (serial debug mode: nothing queued behind an undecided iteration)
-    const bool damped = d_damp != nullptr;
-    const double atol = 1e-6, btol = damped ? 0.5 : 1e-6, conlim = 1e8;  // lsmr.jl:54, il:255
-    const long long rows = (sharded ? s->global_rows : (long long)m) + (damped ? n : 0);
-    const int maxiter = (int)std::max<long long>(rows, n);               // lsmr.jl:55
-    const unsigned epoch = (++c->mail_epoch) & 0x7fffffu;
-    LsmrState *st = s->d_state;
-    const int *done = &st->done;
-    double *xs = s->d_rhs;
-    double *pu = s->d_red, *pv = s->d_red + 4096;   // deferred-reduction partials (sum u~^2 / sum v~^2)
-    // sum(u~x^2) partials are double-buffered: K3 reads iteration k's while writing k+1's
-    double *pxb[2] = {s->d_red + 2 * 4096, s->d_red + 3 * 4096};
-    int *npu = (int *)(s->d_red + 4 * 4096), *npv = npu + 1;
-    int *npxb[2] = {npu + 2, npu + 3};
-
+    LsmrWork W;
+    W.s = s; W.c = c; W.J = J; W.d_y = d_y; W.d_x = d_x; W.m = m; W.n = n;
+    W.damped = d_damp != nullptr; W.sharded = sharded;
+    W.atol = 1e-6; W.btol = W.damped ? 0.5 : 1e-6; W.conlim = 1e8;      // lsmr.jl:54, il:255
+    const long long rows = (sharded ? s->global_rows : (long long)m) + (W.damped ? n : 0);
+    W.maxiter = (int)std::max<long long>(rows, n);                       // lsmr.jl:55
+    W.lookahead = lsq_dbg_serial ? 1 : LSQ_LOOKAHEAD_DEFAULT;   // (serial debug mode: nothing queued behind an undecided iteration)
+    W.epoch = (++c->mail_epoch) & 0x7fffffu;
     if (J->kind == LSQ_MAT_CSC) LSQ_TRY(lsq_ensure_csr(J));
-    // The three-launch iteration (lsq_lsmr3.h): both sliced layouts, x resident in LDS, one rank.  Otherwise K1 | K2 | K3 below.
+    // The three-launch iteration (lsq_lsmr3.h): both sliced layouts, x resident in LDS, one rank.  Otherwise K1 | K2 | K3.
     const bool four_env = getenv("LSQ_LSMR_FOUR_LAUNCHES") != nullptr;      // (read per solve: the tests flip it)
-    const bool fused = !four_env && !sharded && J->kind == LSQ_MAT_CSC && J->srows.active && J->srows.ncw == 1 && J->scols.active &&
-                       n >= 1 && m >= 1 && c->num_cus >= 8;
+    W.fused = !four_env && !sharded && J->kind == LSQ_MAT_CSC && J->srows.active && J->srows.ncw == 1 && J->scols.active &&
+              n >= 1 && m >= 1 && c->num_cus >= 8;
+    W.gn = nvec_grid(c, n); W.dgk = W.damped ? s->d_dg : nullptr;
+    W.tail = tail;
+    W.dynamic = tail && tail->fn && tail->dynamic && !sharded;
+    W.spec = tail && tail->fn && !sharded && (tail->predict > 0 || W.dynamic);
+    W.stb[0] = s->d_state; W.stb[1] = s->d_state + 1;
+    W.pv = s->d_red + 4096;
+    W.pxb[0] = s->d_red + 2 * 4096; W.pxb[1] = s->d_red + 3 * 4096;
+    int *const counts = (int *)(s->d_red + 4 * 4096);               // npu, npv, npx[2]
+    W.npv = counts + 1; W.npxb[0] = counts + 2; W.npxb[1] = counts + 3;
     double *const f3 = s->d_f3;
-    double *const fx[2] = {xs, f3}, *const fhbar[2] = {s->d_hbar, f3 + n}, *const fh[2] = {s->d_h, f3 + 2 * (size_t)n};
-    double *const fw = f3 + 3 * (size_t)n;                          // gather vector of the next J*v: (v~ .* P) .* s
-    double *const fpu[2] = {f3 + 4 * (size_t)n, f3 + 4 * (size_t)n + 4096};
-    int *const fnpu = (int *)(fpu[1] + 4096);                      // two counts
-    LsmrHandoff *const fho = (LsmrHandoff *)(fpu[1] + 4096 + 8);   // the in-launch record of k_lsmr_fused
-    double *const vset = fused ? s->d_t : s->d_v;                  // where the setup (and every K2) leaves v~
-    if (fused) { pu = fpu[0]; npu = fnpu; }
+    W.fx[0] = s->d_rhs; W.fx[1] = f3; W.fhbar[0] = s->d_hbar; W.fhbar[1] = f3 + n; W.fh[0] = s->d_h; W.fh[1] = f3 + 2 * (size_t)n;
+    W.fw = f3 + 3 * (size_t)n;
+    W.fpu[0] = f3 + 4 * (size_t)n; W.fpu[1] = W.fpu[0] + 4096;
+    W.fnpu = (int *)(W.fpu[1] + 4096); W.fho = (LsmrHandoff *)(W.fpu[1] + 4096 + 8);
+    W.vset = W.fused ? s->d_t : s->d_v;
+    W.pu = W.fused ? W.fpu[0] : s->d_red;
+    W.npu = W.fused ? W.fnpu : counts;
     // computed once per Jacobian (reference: twice); row-sharded: the sum over the ranks' blocks -- the preconditioner is a
     // replicated n-vector and has to be the same on every rank
     const double *colsum = nullptr;
@@ -686,431 +1089,15 @@ int lsq_lsmr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, double *d_damp,
         }
     }
     *(volatile unsigned long long *)c->h_mail = 0ull;
-    const int gn = nvec_grid(c, n);
-    const double *dgk = damped ? s->d_dg : nullptr;
-    EpiV ev{done, 0, st, pu, npu, nullptr, nullptr, s->d_P, damped ? s->d_dg : nullptr, nullptr, s->d_v, pv, npv,
-            nullptr, 0.0, 0.0, 0, 0};
-    auto launch_begin = [&]() {
-        long long gb = std::min<long long>(lsq_div_up(m > 0 ? m : 1, LSQ_NT), (long long)c->num_cus * 8);
-        if (gb > 4096) gb = 4096;
-        LSQ_LAUNCH(k_lsmr_begin, dim3((int)gb), dim3(LSQ_NT), 0, c->stream, m, d_y, st, pu, npu, atol,
-                           btol, 1.0 / conlim, maxiter, epoch);
-    };
-    if (lm) {
-        if (!(d_Jty && y_sumsq >= 0.0 && damped && lsq_lsmr_takes_lm_prep(s, J))) {
-            lsq_set_error("lsmr: LM preparation requested where it does not apply");
-            return LSQ_EARG;
-        }
-        LSQ_LAUNCH(k_lm_lsmr_setup, dim3(lsq_div_up(n, 1024)), dim3(1024), 0, c->stream, n, *lm, d_damp, s->d_P, s->d_dg,
-                           s->d_ux, d_Jty, vset, st, pu, npu, y_sumsq, pv, npv, atol, btol, 1.0 / conlim, maxiter, epoch,
-                           (const double *)(fused ? J->d_colscale : nullptr), (double *)(fused ? fw : nullptr));
-        if (!fused)
-        LSQ_LAUNCH(k_lsmr_update, dim3(gn), dim3(LSQ_NT), 0, c->stream, n, st, c->d_mail, pu, npu, pv, npv,
-                           (const double *)nullptr, (const int *)nullptr, pxb[0], npxb[0], dgk, s->d_ux, s->d_P,
-                           s->d_v, s->d_h, s->d_hbar, xs, d_x, s->d_t, c->d_partials, lsq_ctr(c, 3));
-        LSQ_HIP(hipGetLastError());
-    } else if (d_Jty) {
-        if (!(y_sumsq >= 0.0)) launch_begin();
-        LSQ_LAUNCH(k_lsmr_setup, dim3(gn), dim3(LSQ_NT), 0, c->stream, n, colsum, d_damp, s->d_P, s->d_dg,
-                           s->d_ux, d_Jty, vset, st, pu, npu, y_sumsq >= 0.0 ? y_sumsq : -1.0, pv, npv, atol, btol,
-                           1.0 / conlim, maxiter, epoch, custom_p, (const double *)(fused ? J->d_colscale : nullptr),
-                           (double *)(fused ? fw : nullptr));
-        if (!fused)
-        LSQ_LAUNCH(k_lsmr_update, dim3(gn), dim3(LSQ_NT), 0, c->stream, n, st, c->d_mail, pu, npu, pv, npv,
-                           (const double *)nullptr, (const int *)nullptr, pxb[0], npxb[0], dgk, s->d_ux, s->d_P,
-                           s->d_v, s->d_h, s->d_hbar, xs, d_x, s->d_t, c->d_partials, lsq_ctr(c, 3));
-        LSQ_HIP(hipGetLastError());
-    } else {
-        LSQ_LAUNCH(k_lsmr_prep, dim3(gn), dim3(LSQ_NT), 0, c->stream, n, colsum, d_damp, s->d_P,
-                           s->d_dg, s->d_ux, custom_p);
-        launch_begin();
-        LSQ_HIP(hipGetLastError());
-        // v~ = A'u (setup), then K3 in "first" mode
-        if (fused) { ev.vout = vset; ev.cs = J->d_colscale; ev.wout = fw; }
-        if (sharded) LSQ_TRY(rowshard_adjoint(s, J, d_y, ev, pu, npu));
-        else LSQ_TRY(launch_product(J, 1, d_y, ev));
-        // setup K3: u~x is still zero, so only sum(u~_y^2) enters beta_1; it already forms iteration 1's u~x
-        if (!fused)
-        LSQ_LAUNCH(k_lsmr_update, dim3(gn), dim3(LSQ_NT), 0, c->stream, n, st, c->d_mail,
-                           sharded ? (const double *)(s->d_xbuf + n) : (const double *)pu, sharded ? (const int *)s->d_one : (const int *)npu, pv, npv,
-                           (const double *)nullptr, (const int *)nullptr, pxb[0], npxb[0], dgk, s->d_ux, s->d_P,
-                           s->d_v, s->d_h, s->d_hbar, xs, d_x, s->d_t, c->d_partials, lsq_ctr(c, 3));
-        LSQ_HIP(hipGetLastError());
-    }
+    LSQ_TRY(lsmr_enqueue_setup(W, d_damp, d_Jty, y_sumsq, lm, colsum, custom_p));
 
-    int enq = 0, it = 0, istop = 0;
-    bool finished = false;
-    if (fused) {
-        // ---------------------------------------------------------------------------------------------------------------
-        // three launches per inner iteration: K1' (k_lsmr_fused: decides iteration j-1, updates the n-vectors, J*v of
-        // iteration j) | K2a (k_sell_cols) | K2b (k_combine<EpiV>).  Launch j of K1' reads state / partials / x, hbar, h
-        // number (j-1)&1 and writes number j&1; it reports iteration j-1 in the progress word.
-        // ---------------------------------------------------------------------------------------------------------------
-        static const bool no_dynamic3 = getenv("LSQ_NO_DYNAMIC_TAIL") != nullptr;
-        const bool dynamic = tail && tail->fn && tail->dynamic && !no_dynamic3;
-        const bool spec = tail && tail->fn && (tail->predict > 0 || dynamic);
-        int planned = spec ? tail->predict : 0;
-        int tail_at = 0, tail_ran_at = 0, hint_it = 0;
-        // REACT instead of PRE-PLACE (round 6, LSQ_TAIL_REACT; profiles/r06/ab_tail_react.txt).  A guarded tail queued behind the
-        // launch that is expected to commit the stop costs nothing when the guess holds, but ~50 us when it does not: five
-        // launches of full grids that skip themselves stand between the solve's next product and the queue's head (measured:
-        // perfect first guesses would gain 3.6 % on C4, LSQ_TAIL_ORACLE_SEQ).  In this mode the expected stop only makes that
-        // launch CAUTIOUS, and nothing more is queued until it has reported (~8 us into it): if the solve is over the host
-        // queues the tail, unguarded, while the cautious launch winds down; if not, the product of that launch is still
-        // streaming for 20 us and the next launches are queued behind it as usual.  A wrong guess then costs a late product.
-        static const bool react = [] { const char *e = getenv("LSQ_TAIL_REACT"); return e ? atoi(e) != 0 : LSQ_TAIL_REACT_DEFAULT; }();
-        int wait_at = 0;             // react: the iteration whose commit (by a cautious launch) is awaited before anything else is queued
-        bool wait_is_guess = false;  //   ... and that launch was cautious because of a PREDICTION (counted), not only because nothing was known
-        double t1_prev = -1.0, t2_prev = -1.0, ratio2 = s->lsmr_ratio2;
-        LsmrState *stb[2] = {s->d_state, s->d_state + 1};
-        const LsqSell &S = J->srows;
-        const int nxpad = (n + 1) & ~1;
-        const size_t lds = (size_t)(nxpad + LSQ_SELL_ROWS_MAX) * sizeof(double);
-        LSQ_TRY(lsq_set_lds(c, (const void *)k_lsmr_fused<0>, (LSQ_LDS_X_MAX + LSQ_SELL_ROWS_MAX) * sizeof(double)));
-        // update workgroups: the CUs the sliced rows leave without a block (C4: 253 blocks on 256 CUs -> 3), at least 3
-        int ub = c->num_cus - S.nblocks;
-        ub = ub < 3 ? 3 : (ub > LSQ_FUSED_UB_MAX ? LSQ_FUSED_UB_MAX : ub);
-        const int pb = std::max(1, std::min(S.nblocks, c->num_cus - ub));
-        int k1 = 0;                  // K1' launches enqueued: enq (whole iterations) or enq + 1
-        bool need_product = false;   // launch k1 went out commit-only: its product half is still owed (if the solve goes on)
-        static const bool use_halves = getenv("LSQ_LSMR_HALVES") != nullptr;          // (A/B: commit-only + product-only launches)
-        static const bool no_cautious = getenv("LSQ_LSMR_NO_CAUTIOUS") != nullptr;    // (A/B: always the plain fused launch)
-        const int test_no_record = getenv("LSQ_TEST_EXCHANGE_TIMEOUT") ? 1 : 0;       // (read once per solve, not per launch)
-        const size_t prof_base3[2] = {c->prof_ev[0].size(), c->prof_ev[1].size()};
-        std::vector<int> prof_it3[2];
-        unsigned long long spins = 0;
-        // mode 0: the whole launch; 1: commit-only (update workgroups); 2: product-only, the half that a commit-only launch left out;
-        // 3: the whole launch, cautious (the product workgroups wait for the decision before they stream)
-        auto launch_k1 = [&](int mode) -> int {
-            const int j = mode == 2 ? k1 : k1 + 1, in = (j - 1) & 1, out = j & 1;
-            LsmrFused a;
-            a.st_in = stb[in]; a.st_out = stb[out]; a.mail = c->d_mail;
-            a.pu_in = fpu[in]; a.npu_in = fnpu + in; a.pu_out = fpu[out]; a.npu_out = fnpu + out;
-            a.px_in = (damped && j > 1) ? pxb[in] : nullptr; a.npx_in = npxb[in];
-            a.px_out = pxb[out]; a.npx_out = npxb[out];
-            a.pv = pv; a.npv = npv;
-            a.vt = vset; a.w = fw; a.P = s->d_P; a.dg = dgk;
-            a.h_in = fh[in]; a.hbar_in = fhbar[in]; a.x_in = fx[in];
-            a.h_out = fh[out]; a.hbar_out = fhbar[out]; a.x_out = fx[out];
-            a.v = s->d_v; a.xout = d_x; a.ux = s->d_ux;
-            a.uold = j == 1 ? d_y : s->d_u; a.unew = s->d_u;
-            a.n = n; a.ub = mode == 2 ? 0 : ub;
-            a.cautious = mode == 3 ? 1 : 0;
-            a.test_no_record = test_no_record;                      // (test hook: the in-launch hand-off fails)
-            a.ho = fho;
-            a.tag_prev = j > 1 ? s->f3_tag : 0u;                    // (mode 2 has no update workgroups: unused there)
-            if (mode != 2 && ++s->f3_tag == 0u) s->f3_tag = 1u;    // a counter per solver (= per record buffer): every older record
-            a.tag = s->f3_tag;                                      // carries another value; 0 is the zeroed buffer
-            if (mode == 2) a.st_in = stb[out];                      // (the state its commit-only half has committed)
-            const int grid = mode == 1 ? ub : (mode == 2 ? pb : pb + ub);
-            if (mode != 1 && (c->prof_kernels & 1)) lsq_prof_mark(c, 0, 0);
-            hipEvent_t e0, e1;
-            if (mode != 1 && lsq_prof_take(c, &e0, &e1)) {
-                LSQ_LAUNCH_TIMED(k_lsmr_fused<0>, dim3(grid), dim3(LSQ_BIG_NT), lds, c->stream, e0, e1, 0, sell_dev(S), S.wrows, m, nxpad, a);
-                prof_it3[0].push_back(j);
-            } else {
-                LSQ_LAUNCH(k_lsmr_fused<0>, dim3(grid), dim3(LSQ_BIG_NT), lds, c->stream, sell_dev(S), S.wrows, m, nxpad, a);
-            }
-            if (mode != 1 && (c->prof_kernels & 1)) lsq_prof_mark(c, 0, 1);
-            LSQ_HIP(hipGetLastError());
-            if (mode != 2) ++k1;
-            need_product = mode == 1;
-            return LSQ_OK;
-        };
-        auto launch_k2 = [&]() -> int {      // K2 of iteration enq + 1 (its K1' is launch k1 == enq + 1)
-            const int j = enq + 1, cur = j & 1;
-            EpiV e2{&stb[cur]->done, 0, stb[cur], fpu[cur], fnpu + cur, damped ? pxb[cur] : nullptr, npxb[cur], s->d_P, dgk,
-                    damped ? s->d_ux : nullptr, s->d_v, pv, npv, nullptr, 0.0, 0.0, 0, 0};
-            e2.vout = vset; e2.cs = J->d_colscale; e2.wout = fw;
-            if (c->prof_kernels & 2) lsq_prof_mark(c, 1, 0);
-            const size_t before = c->prof_ev[1].size();
-            LSQ_TRY(launch_sell_cols<false>(J, s->d_u, &stb[cur]->done));
-            if (c->prof_ev[1].size() > before) prof_it3[1].push_back(j);
-            if (c->prof_kernels & 2) lsq_prof_mark(c, 1, 1);
-            const int nb = lsq_div_up(n, LSQ_CMB_COLS);
-            LSQ_LAUNCH((k_combine<EpiV>), dim3(std::min(nb, 2048)), dim3(LSQ_NT), 0, c->stream, J->scols.d_part, n, J->scols.ngw, e2, nb,
-                       J->d_colscale);
-            LSQ_HIP(hipGetLastError());
-            ++enq;
-            return LSQ_OK;
-        };
-        while (!finished) {
-            unsigned long long w = *(volatile unsigned long long *)c->h_mail;
-            const bool reported = (unsigned)(w >> 41) == epoch;
-            if (reported) {
-                it = (int)(w & 0xffffffffu);
-                if ((w >> 40) & 1ull) {
-                    istop = (int)((w >> 32) & 0xff);
-                    finished = true;
-                    break;
-                }
-            }
-            if (spec && reported && tail_at > 0 && it >= tail_at) {   // that tail found the solve unfinished and skipped itself
-                c->tail_spec[0]++;
-                c->tail_spec[1]++;
-                tail_at = 0;
-                planned = 0;
-            }
-            if (wait_at > 0 && reported && it >= wait_at) {           // react: the cautious launch found the solve unfinished
-                if (wait_is_guess) {
-                    c->tail_spec[0]++;
-                    c->tail_spec[1]++;
-                    planned = 0;
-                }
-                wait_at = 0;
-            }
-            if (dynamic && reported && it > hint_it && it >= 1) {
-                const double h1 = c->h_mail->test1, h2 = c->h_mail->test2;
-                const unsigned long long w2 = *(volatile unsigned long long *)c->h_mail;
-                if (w2 == w && h1 > 0.0 && h2 > 0.0) {
-                    if (t2_prev > 0.0 && h2 < t2_prev) ratio2 = std::min(0.95, std::max(1e-4, h2 / t2_prev));
-                    int k = 1 << 20;
-                    if (h2 > atol && ratio2 < 1.0) k = std::min(k, (int)std::ceil(std::log(atol / h2) / std::log(ratio2) - 1e-9));
-                    if (t1_prev > 0.0 && h1 < 0.98 * t1_prev && h1 > btol)
-                        k = std::min(k, (int)std::ceil(std::log(btol / h1) / std::log(h1 / t1_prev) - 1e-9));
-                    if (k < (1 << 20) && tail_at == 0) planned = it + std::max(1, k);
-                    t1_prev = h1; t2_prev = h2; hint_it = it;
-                }
-            }
-            // a guarded tail sits behind the commit of iteration tail_at / react: a cautious launch is deciding iteration wait_at
-            const bool hold = (tail_at > 0 && it < tail_at) || (wait_at > 0 && it < wait_at);
-            if (!hold) {
-                if (k1 == enq + 1 && need_product) {             // the tail behind a commit-only launch skipped itself: the solve goes on
-                    LSQ_TRY(launch_k1(2));
-                    spins = 0;
-                    continue;
-                }
-                if (k1 == enq + 1) {                             // the rest of iteration enq + 1
-                    if (!react && spec && tail_at == 0 && planned > 0 && enq >= planned && enq >= 1 && enq > it) {
-                        // (the prediction arrived between the two halves: the launch that commits its iteration is the newest one)
-                        LSQ_TRY(tail->fn(&stb[k1 & 1]->notdone, tail->user));
-                        tail_at = enq;
-                        continue;
-                    }
-                    LSQ_TRY(launch_k2());
-                    spins = 0;
-                    continue;
-                }
-                // K1' number enq + 1 commits iteration enq: it does not count against the look-ahead (nothing is decided without it)
-                if (enq - it < lookahead + 1 && enq < maxiter + 1) {
-                    // the caller's tail right behind the launch that commits the planned last iteration (or the newest one, if
-                    // the prediction names an iteration whose commit is already in the queue) -- and that launch commit-only: if
-                    // the plan holds there is no next product
-                    const bool place = spec && tail_at == 0 && planned > 0 && enq >= planned && enq >= 1;
-                    // ... and cautious also where nothing is known yet: the launch that decides iteration 1, unless the previous
-                    // solve was a long one
-                    const bool unknown = spec && enq == 1 && hint_it == 0 && tail->predict <= 3;
-                    const int mode = no_cautious ? 0 : (place ? (use_halves ? 1 : 3) : (unknown && !use_halves ? 3 : 0));
-                    LSQ_TRY(launch_k1(mode));
-                    if (react && mode == 3) {                    // nothing behind it until it has decided
-                        wait_at = enq;
-                        wait_is_guess = place;
-                    } else if (place) {
-                        LSQ_TRY(tail->fn(&stb[k1 & 1]->notdone, tail->user));
-                        tail_at = enq;
-                    }
-                    spins = 0;
-                    continue;
-                }
-            }
-            if (c->idle_hook) lsq_run_idle_hook(c);
-            if ((++spins & 0x3ffu) != 0) continue;
-            const hipError_t sq = hipStreamQuery(c->stream);
-            if (sq != hipSuccess && sq != hipErrorNotReady) {
-                lsq_set_error("HIP error inside the LSMR iteration: %s", hipGetErrorString(sq));
-                return LSQ_EHIP;
-            }
-            if (sq == hipSuccess) {
-                w = *(volatile unsigned long long *)c->h_mail;
-                if ((unsigned)(w >> 41) == epoch && ((w >> 40) & 1ull)) continue;
-                if ((unsigned)(w >> 41) == epoch && (int)(w & 0xffffffffu) >= k1 - 1) continue;
-                LsmrState hs;      // mailbox not visible (should not happen with coherent host memory): read the state
-                LSQ_HIP(hipMemcpy(&hs, stb[k1 & 1], sizeof(hs), hipMemcpyDeviceToHost));
-                it = hs.iter;
-                if (hs.done) {
-                    istop = hs.istop;
-                    finished = true;
-                } else if (enq >= maxiter + 1) {
-                    lsq_set_error("lsmr: iteration budget exhausted without a stop rule");
-                    return LSQ_EHIP;
-                }
-            }
-        }
-        for (int k = 0; k < 2; ++k) {     // timed launches queued beyond the stop did no work: drop their samples
-            auto &v = c->prof_ev[k];
-            const int last_working = k == 0 ? it + 1 : it;   // K1' number it + 1 committed the stop but skipped its product
-            while (v.size() > prof_base3[k] && !prof_it3[k].empty() && prof_it3[k].back() > (k == 0 ? last_working - 1 : last_working)) {
-                hipEventDestroy(v.back()); v.pop_back();
-                hipEventDestroy(v.back()); v.pop_back();
-                prof_it3[k].pop_back();
-            }
-        }
-        if (istop == 99) {     // (a product workgroup gave up waiting for workgroup 0's record: lsq_lsmr3.h)
-            lsq_set_error("lsmr: the in-launch hand-off of k_lsmr_fused timed out");
-            return LSQ_EHIP;
-        }
-        s->last_iter = it;
-        s->last_istop = istop;
-        if (nmul) *nmul = 2 * it;
-        if (tail_at > 0) {
-            c->tail_spec[0]++;
-            if (it > tail_at) c->tail_spec[1]++;
-            else tail_ran_at = tail_at;
-        }
-        if (wait_at > 0 && wait_is_guess) c->tail_spec[0]++;      // react: the predicted stop was the stop (a right guess)
-        if (dynamic && t2_prev > 0.0) s->lsmr_ratio2 = ratio2;
-        if (tail && tail->fn && tail_ran_at == 0) LSQ_TRY(tail->fn(nullptr, tail->user));
-        return LSQ_OK;
-    }
-
-    EpiU eu{done, 0, st, d_y, s->d_u, n, s->d_dg, s->d_t, s->d_ux, pu, npu, nullptr, 0.0};
-    ev.ux = damped ? s->d_ux : nullptr;
-
-    // Where the caller's tail goes (LsmrTail, lsq_solver.h).  `planned`: the iteration behind which it should be queued --
-    // first the caller's guess (the previous solve's count), from iteration 1 on the solve's own prediction: the hints K3
-    // publishes are test1 = |r|/|b| and test2 = |A'r|/(|A||r|); a solve is over when test1 <= btol (+ a 1e-6-sized term) or
-    // test2 <= atol (lsmr.jl:224-231; the other rules do not fire on these operators), and on the damped, Jacobi-
-    // preconditioned operators of an LM run test2 falls geometrically (C4: x 0.07-0.09 per iteration, every iteration).
-    static const bool no_dynamic = getenv("LSQ_NO_DYNAMIC_TAIL") != nullptr;
-    const bool dynamic = tail && tail->fn && tail->dynamic && !sharded && !no_dynamic;
-    const bool spec = tail && tail->fn && !sharded && (tail->predict > 0 || dynamic);
-    int planned = spec ? tail->predict : 0;
-    int tail_at = 0;             // iteration behind which the latest guarded tail was enqueued (0: none that is still undecided)
-    int tail_ran_at = 0;         // ... and the same once it is known (or bound) to have run: the stop iteration was <= tail_at
-    int hint_it = 0;             // last iteration whose hints went into the prediction
-    double t1_prev = -1.0, t2_prev = -1.0, ratio2 = s->lsmr_ratio2;
-    const size_t prof_base[2] = {c->prof_ev[0].size(), c->prof_ev[1].size()};
-    std::vector<int> prof_iter[2];   // iteration number of every timed launch of this solve
-    unsigned long long spins = 0;
-    while (!finished) {
-        unsigned long long w = *(volatile unsigned long long *)c->h_mail;
-        if ((unsigned)(w >> 41) == epoch) {
-            it = (int)(w & 0xffffffffu);
-            if ((w >> 40) & 1ull) {
-                istop = (int)((w >> 32) & 0xff);
-                finished = true;
-                break;
-            }
-        }
-        const bool reported_now = (unsigned)(w >> 41) == epoch;
-        if (spec && reported_now && tail_at > 0 && it >= tail_at) {   // (not done: `finished` left the loop above)
-            // the tail behind iteration tail_at found the solve unfinished and skipped itself: a wrong guess
-            c->tail_spec[0]++;
-            c->tail_spec[1]++;
-            tail_at = 0;
-            planned = 0;
-        }
-        if (dynamic && reported_now && it > hint_it && it >= 1) {
-            const double h1 = c->h_mail->test1, h2 = c->h_mail->test2;
-            const unsigned long long w2 = *(volatile unsigned long long *)c->h_mail;
-            if (w2 == w && h1 > 0.0 && h2 > 0.0) {        // (the pair belongs to iteration `it`: the word did not move meanwhile)
-                if (t2_prev > 0.0 && h2 < t2_prev) ratio2 = std::min(0.95, std::max(1e-4, h2 / t2_prev));
-                int k = 1 << 20;
-                if (h2 > atol && ratio2 < 1.0) k = std::min(k, (int)std::ceil(std::log(atol / h2) / std::log(ratio2) - 1e-9));
-                if (t1_prev > 0.0 && h1 < 0.98 * t1_prev && h1 > btol)       // test1 still falling: when does it reach btol?
-                    k = std::min(k, (int)std::ceil(std::log(btol / h1) / std::log(h1 / t1_prev) - 1e-9));
-                if (k < (1 << 20) && tail_at == 0) planned = it + std::max(1, k);
-                t1_prev = h1; t2_prev = h2; hint_it = it;
-            }
-        }
-        // the guarded tail: right behind the planned last iteration, as soon as that one is enqueued (or behind the newest
-        // enqueued, still unreported one if the prediction names an iteration that is already in the queue)
-        if (spec && tail_at == 0 && planned > 0 && enq >= planned && enq > it) {
-            LSQ_TRY(tail->fn(&st->notdone, tail->user));
-            tail_at = enq;
-        }
-        // Row-sharded: every rank must enqueue the SAME number of inner iterations (each carries a collective), so the count
-        // cannot depend on when this host happens to see the mailbox: iterations go out in chunks of `lookahead`, and the
-        // next chunk only once the last one has reported "not done" -- ceil(stop / lookahead) * lookahead on every rank.
-        // (and the first chunk only once the SETUP has reported: a solve that is over before it starts -- A'b = 0 -- must not
-        //  get a chunk on the ranks whose host looked too early)
-        const bool reported = (unsigned)(w >> 41) == epoch;
-        // (a speculative tail sits behind iteration tail_at: nothing more is queued until that iteration has reported)
-        const bool hold = tail_at > 0 && enq == tail_at && it < tail_at;
-        const bool want = sharded ? (reported && enq == it && enq < maxiter) : (!hold && enq - it < lookahead && enq < maxiter);
-        if (want) {
-          const int chunk = sharded ? (int)std::min<long long>(lookahead, (long long)maxiter - enq) : 1;
-          for (int q = 0; q < chunk; ++q) {
-            if (c->prof_kernels & 1) lsq_prof_mark(c, 0, 0);
-            {
-                const size_t before = c->prof_ev[0].size();
-                LSQ_TRY(launch_product(J, 0, s->d_t, eu));   // K1
-                if (c->prof_ev[0].size() > before) prof_iter[0].push_back(enq + 1);
-            }
-            if (c->prof_kernels & 1) lsq_prof_mark(c, 0, 1);
-            eu.uold = s->d_u;                            // after the first iteration u~ lives in d_u
-            const int cur = enq & 1;                     // px buffer holding this iteration's sum(u~x^2)
-            ev.px = damped ? pxb[cur] : nullptr;
-            ev.npx = npxb[cur];
-            if (c->prof_kernels & 2) lsq_prof_mark(c, 1, 0);
-            {
-                const size_t before = c->prof_ev[1].size();
-                if (sharded) LSQ_TRY(rowshard_adjoint(s, J, s->d_u, ev, pu, npu));   // K2 with the ranks' sum in the middle
-                else LSQ_TRY(launch_product(J, 1, s->d_u, ev));   // K2
-                if (c->prof_ev[1].size() > before) prof_iter[1].push_back(enq + 1);
-            }
-            if (c->prof_kernels & 2) lsq_prof_mark(c, 1, 1);
-            LSQ_LAUNCH(k_lsmr_update, dim3(gn), dim3(LSQ_NT), 0, c->stream, n, st, c->d_mail,
-                               sharded ? (const double *)(s->d_xbuf + n) : (const double *)pu,
-                               sharded ? (const int *)s->d_one : (const int *)npu,
-                               pv, npv, (const double *)(damped ? pxb[cur] : nullptr), (const int *)npxb[cur],
-                               pxb[cur ^ 1], npxb[cur ^ 1], dgk, s->d_ux, s->d_P, s->d_v, s->d_h, s->d_hbar, xs,
-                               d_x, s->d_t, c->d_partials, lsq_ctr(c, 3));
-            LSQ_HIP(hipGetLastError());
-            ++enq;
-          }
-            spins = 0;
-            continue;
-        }
-        if (c->idle_hook) lsq_run_idle_hook(c);   // look-ahead window full: the device has work for a while
-        if ((++spins & 0x3ffu) != 0) continue;
-        const hipError_t sq = hipStreamQuery(c->stream);
-        if (sq != hipSuccess && sq != hipErrorNotReady) {   // launch failure / device fault: the mailbox will never move
-            lsq_set_error("HIP error inside the LSMR iteration: %s", hipGetErrorString(sq));
-            return LSQ_EHIP;
-        }
-        if (sq == hipSuccess) {
-            // stream drained: whatever the mailbox shows now is final for the enqueued work
-            w = *(volatile unsigned long long *)c->h_mail;
-            if ((unsigned)(w >> 41) == epoch && ((w >> 40) & 1ull)) continue;
-            if ((unsigned)(w >> 41) == epoch && (int)(w & 0xffffffffu) >= enq) continue;
-            // mailbox not visible (should not happen with coherent host memory): read the state
-            LsmrState hs;
-            LSQ_HIP(hipMemcpy(&hs, st, sizeof(hs), hipMemcpyDeviceToHost));
-            it = hs.iter;
-            if (hs.done) {
-                istop = hs.istop;
-                finished = true;
-            } else if (enq >= maxiter) {
-                lsq_set_error("lsmr: iteration budget exhausted without a stop rule");
-                return LSQ_EHIP;
-            }
-        }
-    }
-    // instrumentation: launches queued beyond the stopping iteration returned on their first
-    // instruction -- drop their samples so the reported average is over working launches only
-    for (int k = 0; k < 2; ++k) {
-        auto &v = c->prof_ev[k];
-        // sample j of this solve (j = 0, 1, ...) belongs to iteration prof_iter[k][j] (1-based)
-        while (v.size() > prof_base[k] && !prof_iter[k].empty() && prof_iter[k].back() > it) {
-            hipEventDestroy(v.back());
-            v.pop_back();
-            hipEventDestroy(v.back());
-            v.pop_back();
-            prof_iter[k].pop_back();
-        }
-    }
-    s->last_iter = it;
-    s->last_istop = istop;
-    if (nmul) *nmul = 2 * it;  // lsmr.jl:236 ch.mvps
-    // the latest guarded tail ran iff the solve was over when its kernels reached the device: stop iteration <= tail_at
-    // (tails that skipped themselves were counted, as wrong guesses, when their iteration reported)
-    if (tail_at > 0) {
-        c->tail_spec[0]++;
-        if (it > tail_at) c->tail_spec[1]++;
-        else tail_ran_at = tail_at;
-    }
-    if (dynamic && t2_prev > 0.0) s->lsmr_ratio2 = ratio2;
-    if (tail && tail->fn && tail_ran_at == 0) LSQ_TRY(tail->fn(nullptr, tail->user));
+    StopPredictor pred{-1.0, -1.0, s->lsmr_ratio2, 0};
+    LsmrRun r;
+    LSQ_TRY(W.fused ? lsmr_run_fused(W, pred, r) : lsmr_run_four(W, pred, r));
+    s->last_iter = r.it;
+    s->last_istop = r.istop;
+    if (nmul) *nmul = 2 * r.it;  // lsmr.jl:236 ch.mvps
+    if (W.dynamic && pred.t2_prev > 0.0) s->lsmr_ratio2 = pred.ratio2;
+    if (tail && tail->fn && !r.tail_ran) LSQ_TRY(tail->fn(nullptr, tail->user));
     return LSQ_OK;
 }

@@ -20,10 +20,9 @@
 // with istop = 99 and the host returns LSQ_EHIP).
 // The state and x, hbar, h are double-buffered (launch k reads set (k-1)&1 and writes set k&1): the update workgroups read ALL of
 // x, hbar, h for ||x|| while their siblings write their own thirds; a late workgroup must not read what its own launch commits.
-// Where the host expects the launch to find the solve finished (lsq_lsmr_solve: the predicted last iteration; the first iteration
-// when nothing is known yet) it asks for a CAUTIOUS launch: the product workgroups wait for the record before they stream.  (The
-// launch also comes in halves -- COMMIT-ONLY, grid = the update workgroups, and PRODUCT-ONLY, ub = 0, the record of the commit-only
-// launch already there -- LSQ_LSMR_HALVES=1: the first form of the same idea, kept for A/B.)
+// Where the host expects the launch to find the solve finished (lsmr_run_fused: the predicted last iteration; the first iteration
+// when nothing is known yet) it asks for a CAUTIOUS launch: the product workgroups wait for the record before they stream.  Every
+// launch is the whole grid: update workgroups in front, product workgroups behind them.
 #pragma once
 
 constexpr int LSQ_FUSED_UB_MAX = 4;
@@ -111,7 +110,7 @@ __device__ inline void lsmr_decide(LsmrState &s, double total) {
 constexpr long long LSQ_FUSED_SPIN_LIMIT = 1LL << 24;      // x ~64 cycles of s_sleep: about a second
 
 // The progress word WITHOUT release semantics: a system-scope release makes the storing wave write the L2 back and wait for every
-// store it has in flight (~2 us measured on the critical path of the commit-only launch).  Nothing the host reads on seeing the
+// store it has in flight (~2 us measured on the critical path of the update workgroups).  Nothing the host reads on seeing the
 // word depends on that order: results are read behind a stream synchronisation, and the two hints beside the word only feed a
 // prediction (the host re-reads the word around them; a stale pair costs a wrong guess).
 __device__ __forceinline__ void publish_relaxed(LsqMailbox *mail, const LsmrState *st) {
@@ -160,7 +159,7 @@ __device__ __forceinline__ void ordered_sum512x3(const double *pa, const int *na
 
 // Block reductions for the tail of the update workgroups, where global STORES are in flight: __syncthreads() makes a wave wait for
 // its outstanding stores (vmcnt(0)) before it joins the barrier -- microseconds here (measured: 4.4 us at the last barrier of the
-// commit-only launch) for an exchange that only goes through LDS.  These wait for the LDS counter alone.
+// update workgroups) for an exchange that only goes through LDS.  These wait for the LDS counter alone.
 __device__ __forceinline__ void lsq_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 template <bool IS_MAX>
 __device__ __forceinline__ double lsq_block_reduce_lds(double v, double *sh /* 16 doubles */) {

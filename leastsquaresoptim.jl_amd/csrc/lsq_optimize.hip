@@ -910,29 +910,15 @@ static int optimize_lm_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat 
             return LSQ_OK;
         };
         // (with the per-iteration exchange of independent problems too: the hook is issued by the LSMR driver while the device
-        //  works off the queued iterations and the tail; LSQ_NO_TAIL_WITH_EXCHANGE=1 restores the round-3 exclusion)
-        const bool tail_ok = !exact && !sharded && (!o->allreduce || !getenv("LSQ_NO_TAIL_WITH_EXCHANGE")) && sv->kind == LSQ_LSMR &&
-                             !b.lo && !b.hi;
+        //  works off the queued iterations and the tail)
+        const bool tail_ok = !exact && !sharded && sv->kind == LSQ_LSMR && !b.lo && !b.hi;
         bool tail_done = false;
         if (sv->kind == LSQ_LSMR) {
             const LsmrLmPrep prep{cs, 1.0 / delta, MIN_DIAGONAL, MAX_DIAGONAL, x, b.lo, b.hi, c->d_slots + SL_GRAD};
             // (speculation needs kernels that honour the skip flag: the device model on the sliced rows)
             static const bool no_spec = getenv("LSQ_NO_TAIL_SPECULATION") != nullptr;
             const bool guardable = tc.is_model && J->kind == LSQ_MAT_CSC && J->srows.active && !no_spec && !lsq_dbg_serial;
-            // (diagnostic, LSQ_TAIL_ORACLE_SEQ="1,1,6,5,3,1": the inner counts of a solve that is being REPEATED, fed back as perfect
-            //  first guesses -- the A/B that prices a wrong guess: profiles/r06/ab_tail_oracle.txt; never set in a measured run)
-            static const std::vector<int> oracle_seq = [] {
-                std::vector<int> v;
-                if (const char *e = getenv("LSQ_TAIL_ORACLE_SEQ"))
-                    for (const char *p = e; *p;) {
-                        v.push_back(atoi(p));
-                        while (*p && *p != ',') ++p;
-                        if (*p == ',') ++p;
-                    }
-                return v;
-            }();
-            const int first_guess = oracle_seq.empty() ? last_inner : oracle_seq[(size_t)(iter - 1) % oracle_seq.size()];
-            LsmrTail tail{guardable ? first_guess : 0, tail_fn, &tc, guardable && oracle_seq.empty()};
+            LsmrTail tail{guardable ? last_inner : 0, tail_fn, &tc, guardable};
             LSQ_TRY(lsq_lsmr_solve(sv, J, fcur, b.dtd, b.dx, &lmiter, b.grad, ssr, lm_prep ? &prep : nullptr,
                                    tail_ok ? &tail : nullptr));  // :87
             tail_done = tail_ok;
@@ -944,50 +930,40 @@ static int optimize_lm_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat 
         mul_calls += lmiter;
         inner_total += lmiter / 2;
         double sl[6] = {0, 0, 0, 0, 0, 0};
+        if (!tail_done && !exact && !sharded) {
+            // the solve was not handed the tail (bounds, or a factorisation): the same sequence, unguarded, behind the clipped step
+            LSQ_TRY(lsq_box_clip(c, n, b.dx, x, b.lo, b.hi));                // :89-98
+            LSQ_TRY(tail_fn(nullptr, &tc));
+            tail_done = true;
+        }
         if (tail_done) {
             f_calls++;
             spec_launched = tc.spec_launched;
             LSQ_TRY(lsq_wait_slots(c, SL_GRAD, 6, tc.pub.seq, sl));
         } else {
-        LSQ_TRY(lsq_box_clip(c, n, b.dx, x, b.lo, b.hi));                // :89-98
-        double *t_out = nullptr, *s_out = nullptr;   // (the built-in model takes tanh(x_trial) from this launch)
-        if (!exact && f == model_f) model_trial_buffers(user, xt, &t_out, &s_out);
-        LSQ_LAUNCH(k_step, dim3(gn), dim3(LSQ_NT), 0, c->stream, n, x, b.dx, xt, c->d_partials,
-                           lsq_ctr(c, 5), c->d_slots + SL_DX, c->d_slots + SL_NONFIN, t_out, s_out);   // :106
-        LSQ_HIP(hipGetLastError());
-        if (exact) {
-            CB(f(ftrial, xt, user));                                      // :107
-            f_calls++;
-            LSQ_TRY(sumsq_to_slot(c, exact, m, ftrial, 7, c->d_slots + SL_TRIAL));                 // :111
-            LSQ_TRY(predicted_to_slot(c, exact, J, b.dx, fcur, b.fpred, 8, c->d_slots + SL_PRED));   // :114-117
+            LSQ_TRY(lsq_box_clip(c, n, b.dx, x, b.lo, b.hi));                // :89-98
+            double *t_out = nullptr, *s_out = nullptr;   // (the built-in model takes tanh(x_trial) from this launch)
+            if (!exact && f == model_f) model_trial_buffers(user, xt, &t_out, &s_out);
+            LSQ_LAUNCH(k_step, dim3(gn), dim3(LSQ_NT), 0, c->stream, n, x, b.dx, xt, c->d_partials,
+                               lsq_ctr(c, 5), c->d_slots + SL_DX, c->d_slots + SL_NONFIN, t_out, s_out);   // :106
             LSQ_HIP(hipGetLastError());
-            LSQ_TRY(lsq_read_slots(c, SL_GRAD, 5, sl));   // the one host sync of the outer iteration
-        } else if (sharded) {
-            // the two sums over residual rows are completed across the ranks (one all-reduce of 2 doubles) before the
-            // iteration's scalars go to the host
-            static_assert(SL_PRED == SL_TRIAL + 1, "trial and predicted ssr travel together");
-            LSQ_TRY(predicted_to_slot(c, exact, J, b.dx, fcur, b.fpred, 8, c->d_slots + SL_PRED));
-            LSQ_TRY(f_then_sumsq(c, exact, f, user, m, ftrial, xt, 7, c->d_slots + SL_TRIAL));
-            f_calls++;
-            LSQ_TRY(rows_sum(c->d_slots + SL_TRIAL, 2));
-            LSQ_TRY(lsq_read_slots(c, SL_GRAD, 5, sl));
-        } else {
-            // the predicted residual (:114-117), f!(x_trial) and sum(abs2, ftrial) (:107, :111); the last kernel of the iteration
-            // hands the scalars to the host.  The built-in model on a column-scaled handle takes all of it in one pass over A.
-            LsqSlotPublish pub = lsq_slots_ticket(c, SL_GRAD, 6);
-            bool pair = false;
-            SpecGrad sg{spec_ok ? next_gate(c, b) : nullptr, ssr, b.grad, false};
-            if (f == model_f) CB(model_pair_tail(user, J, b.dx, fcur, ftrial, xt, c->d_slots + SL_PRED, c->d_slots + SL_TRIAL, pub, nullptr, &pair, &sg));
-            spec_launched = sg.launched;
-            if (sg.launched) spec_pending = true;
-            if (!pair) {
+            if (exact) {
+                CB(f(ftrial, xt, user));                                      // :107
+                f_calls++;
+                LSQ_TRY(sumsq_to_slot(c, exact, m, ftrial, 7, c->d_slots + SL_TRIAL));                 // :111
+                LSQ_TRY(predicted_to_slot(c, exact, J, b.dx, fcur, b.fpred, 8, c->d_slots + SL_PRED));   // :114-117
+                LSQ_HIP(hipGetLastError());
+                LSQ_TRY(lsq_read_slots(c, SL_GRAD, 5, sl));   // the one host sync of the outer iteration
+            } else {
+                // row-sharded: the two sums over residual rows are completed across the ranks (one all-reduce of 2 doubles) before
+                // the iteration's scalars go to the host
+                static_assert(SL_PRED == SL_TRIAL + 1, "trial and predicted ssr travel together");
                 LSQ_TRY(predicted_to_slot(c, exact, J, b.dx, fcur, b.fpred, 8, c->d_slots + SL_PRED));
-                LSQ_TRY(f_then_sumsq(c, exact, f, user, m, ftrial, xt, 7, c->d_slots + SL_TRIAL, pub));
+                LSQ_TRY(f_then_sumsq(c, exact, f, user, m, ftrial, xt, 7, c->d_slots + SL_TRIAL));
+                f_calls++;
+                LSQ_TRY(rows_sum(c->d_slots + SL_TRIAL, 2));
+                LSQ_TRY(lsq_read_slots(c, SL_GRAD, 5, sl));
             }
-            f_calls++;
-            LSQ_HIP(hipGetLastError());
-            LSQ_TRY(lsq_wait_slots(c, SL_GRAD, 6, pub.seq, sl));
-        }
         }
         mul_calls++;
         maxabs_gr = sl[0];

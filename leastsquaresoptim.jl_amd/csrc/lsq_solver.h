@@ -197,16 +197,16 @@ struct LsmrLmPrep {
     double *out_grad;
 };
 constexpr int LSMR_LM_PREP_MAX_N = 16384;   // every workgroup of that launch reduces colsum and g over all n itself
-// tail (optional): what the caller will launch once the solve is over and which depends on nothing but d_x.  `predict` > 0:
-// the tail is enqueued right behind inner iteration `predict` with skip = &state->notdone (its kernels return at once if the
-// solve is NOT over by then) and no further iteration is queued until that iteration has reported -- if the prediction holds
-// (the usual case: the inner count of an LM run changes slowly) the device goes from the last inner iteration straight into
-// the caller's next kernels, without the early-exit launches of the look-ahead and without waiting for the host to notice.
-// Otherwise, and always when predict == 0, the tail is called (again) with skip = nullptr after the solve.
-// `dynamic`: from inner iteration 1 on the guess is replaced by a prediction from the solve's own stopping quantities (the
-// hints K3 publishes beside the progress word): on LM's damped, Jacobi-preconditioned operators test2 = |A'r|/(|A||r|) falls
-// geometrically and the iteration at which it crosses atol (or test1 crosses btol) is known one or two iterations ahead; a
-// tail that skipped itself may be queued again, guarded, behind a later iteration.
+// tail (optional): what the caller will launch once the solve is over and which depends on nothing but d_x.  `predict` > 0: a
+// guess at the solve's last inner iteration (the inner count of an LM run changes slowly).  The three-launch iteration
+// (lsmr_run_fused) REACTS: the launch that commits the guessed iteration is cautious, nothing is queued behind it until it has
+// reported, and the tail is called once, with skip = nullptr, after the stop has been seen.  The four-launch iteration
+// (lsmr_run_four) PRE-PLACES: the tail is enqueued right behind inner iteration `predict` with skip = &state->notdone (its
+// kernels return at once if the solve is NOT over by then) and no further iteration is queued until that one has reported; a
+// tail that skipped itself may be queued again, guarded, behind a later iteration, and unless a guarded tail is known to have
+// run the tail is called (again) with skip = nullptr after the solve.  predict == 0, general preconditioner, reference-order
+// kernels: called once after the solve.  `dynamic`: from inner iteration 1 on the guess is replaced by a prediction from the
+// hints beside the progress word (StopPredictor, lsq_lsmr.hip).
 struct LsmrTail {
     int predict = 0;
     int (*fn)(const int *skip, void *user) = nullptr;

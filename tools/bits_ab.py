@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Same-box comparison of two builds of liblsqhip.so (LSQ_LIB_PATH per process): solutions of a few dense solves dumped to .npy"""
 import os, sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import lsq_amd as lsq
 ctx = lsq.Context(0)

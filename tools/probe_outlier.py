@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Which solve of a repeated dense QR ldiv! is slow, and did a bounded wait give up?  (round 6: 17 ms averages at 3000x700 damped)"""
 import os, sys, time
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import lsq_amd as lsq
 ctx = lsq.Context(0)

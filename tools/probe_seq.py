@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """dense_bench's sequence of cases in ONE process with every solve timed (round 6: where do the 17 ms averages at 3000x700 come from?)"""
 import os, sys, time
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import lsq_amd as lsq
 ctx = lsq.Context(0)

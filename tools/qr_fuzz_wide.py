@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Random multi-panel shapes (n up to 1500: many 64-column panels, row groups that do not divide the CUs, panels on either side of
 the 256-slab look-ahead rule) through the dense QR, undamped and damped, against numpy; also the round-5 grid of the trailing
-update (LSQ_QR_UPDATE_FLAT=0 in a second process) must give the same bits.   python tools/r6/qr_fuzz_wide.py <seed> <count> <out.npz>"""
+update (LSQ_QR_UPDATE_FLAT=0 in a second process) must give the same bits.   python tools/qr_fuzz_wide.py <seed> <count> <out.npz>"""
 import os, sys, time
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import lsq_amd as lsq
 ctx = lsq.Context(0)

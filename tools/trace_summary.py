@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Summarise a rocprofv3 kernel_trace.csv: per kernel, all launches and the *working* launches.
 
-LSMR runs at most LSQ_LOOKAHEAD iterations ahead of the device-side stop test; launches queued
+LSMR runs at most two iterations (the look-ahead) ahead of the device-side stop test; launches queued
 behind a finished solve return on their first instruction (3-5 us).  `--stats` averages those
 no-op launches together with the working ones, so this table separates them (for the kernels that can
 exit early, a launch counts as "working" when it lasts longer than 60 % of the kernel's 90th-percentile
@@ -11,7 +11,7 @@ rows = collections.defaultdict(list)
 with open(sys.argv[1]) as fh:
     for r in csv.DictReader(fh):
         name = r["Kernel_Name"]
-        if "k_lsmr_fused" in name:      # the launch comes whole, commit-only (a few workgroups) or product-only: keep them apart
+        if "k_lsmr_fused" in name:      # the grid depends on the Jacobian's sliced rows: keep different shapes apart
             name += " grid=%s" % r.get("Grid_Size", r.get("Grid_Size_X", "?"))
         rows[name].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
 tot = sum(sum(v) for v in rows.values())
