@@ -312,6 +312,49 @@ int lsq_optimize(lsq_ctx *ctx, int optimizer, int solver_kind, lsq_mat *J, doubl
                  double *d_fcur, lsq_f_callback f, lsq_g_callback g, void *user,
                  const lsq_options *opt, lsq_result *res);
 
+/* ---- B independent fits stacked on a block-diagonal Jacobian: one trust region PER BLOCK ----
+ * For every block b of J = blkdiag(J_1 .. J_B) (lsq_blockdiag_create, nb <= 64) this runs the reference's optimize!
+ * (levenberg_marquardt.jl:39-144 / dogleg.jl:41-203 with Cholesky(), dense_cholesky.jl:29-59) on the mb x nb problem made of
+ * residual rows b*mb .. (b+1)*mb-1 and parameters b*nb .. (b+1)*nb-1: its own delta (10 / 1; Dogleg: times wnorm(x_b, dtd_b)
+ * at its first iteration, dogleg.jl:92-97), decrease_factor (levenberg_marquardt.jl:53,136-137) or reuse flag with the cached
+ * Gauss-Newton / gradient steps (dogleg.jl:59-62,81), its own mean of dtd over ITS nb columns (levenberg_marquardt.jl:84-85),
+ * rho, accept / revert, assess_convergence (utils.jl:7-31) and iteration count; f_calls / g_calls / mul_calls are what that
+ * block's own run of the reference would count.  A block that has converged, reached opt->iterations or failed is frozen: its
+ * x_b, fcur_b, ssr and counters never change again and no solve work is done for it; the call returns when no block is active.
+ * x_tol, f_tol, g_tol, iterations, delta apply to every block; h_lower / h_upper are NULL or of length n.
+ * A failure of ONE block does not end the call: its status[b] becomes LSQ_ENOTPD (LM; info[b] = the 1-based column of the
+ * block at which dpotrf stops), LSQ_ERANK (Dogleg; info[b] = the rank of the block's pivoted factorisation) or LSQ_ENONFINITE
+ * (check_isfinite, utils.jl:70-75; info[b] = the first non-finite index inside the block), it keeps the iterate it held and
+ * the others go on; the call returns LSQ_OK.  Callback failures, HIP errors and bad arguments are call-level.
+ * f and g are the callbacks of lsq_optimize on the stacked x (n), residual (m) and lsq_mat_values(J); they must be
+ * block-separable (rows of block b depend on x_b only -- what a block-diagonal Jacobian says) and deterministic.  They are
+ * called once per outer iteration for all blocks: g is handed, for every block that does not need a new Jacobian, the x_b at
+ * which that block's Jacobian was last evaluated (the reference does not re-evaluate J_b at a reverted iterate,
+ * levenberg_marquardt.jl:135), and the trial point holds a frozen block's final x_b; what f writes into the rows of frozen
+ * blocks is ignored.  Refused with LSQ_EARG: a handle that is not block-diagonal, nb > 64, LSQ_QR, LSQ_LSMR, and any of
+ * allreduce / row_allreduce / the preconditioner hooks in the options.
+ * All arrays of the result are HOST arrays owned by the caller, of length B unless said otherwise; any may be NULL.  The
+ * trace (trace_cap > 0 and all six trace pointers set): row k, 0-based, of block b -- [k * B + b], x: [k * n + b * nb ..] --
+ * is that block's state after its iteration k + 1 and only meaningful for k < iterations[b].
+ * `batched_result` points to an lsq_batched_result (spelled void * here: the header lint of tests/julia_shim_lint.py classifies
+ * parameter types from a closed list). */
+typedef struct {
+    double *ssr, *ssr0;         /* sum(abs2, fcur_b) at the end / at x0 */
+    int *iterations;
+    int *converged, *x_converged, *f_converged, *g_converged;
+    int *f_calls, *g_calls, *mul_calls;
+    int *status, *info;         /* lsq_status of the block; info: see above, -1 when there is none */
+    int outer_iterations;       /* out: passes of the device loop = max over the blocks of iterations */
+    double seconds;             /* out: wall time of the loop (host clock, includes syncs) */
+    int trace_cap;              /* in: rows of the trace arrays (0: no trace) */
+    double *trace_ssr, *trace_gnorm, *trace_delta, *trace_rho;   /* trace_cap * B */
+    int *trace_accept;          /* trace_cap * B */
+    double *trace_x;            /* trace_cap * n */
+} lsq_batched_result;
+int lsq_optimize_batched(lsq_ctx *ctx, int optimizer, int solver_kind, lsq_mat *J, double *d_x,
+                         double *d_fcur, lsq_f_callback f, lsq_g_callback g, void *user,
+                         const lsq_options *opt, void *batched_result);
+
 /* ---- built-in device-side model for the synthetic benchmarks:
  *      r(x) = A tanh(x) - b,  J = A diag(1 - tanh(x)^2); A has J's pattern. ---- */
 int lsq_model_tanh_create(lsq_ctx *ctx, lsq_mat *J, const double *h_Avalues, const double *h_b,

@@ -54,6 +54,16 @@ class Result(C.Structure):
                 ("seconds", C.c_double), ("lsmr_iterations", C.c_longlong), ("ssr0", C.c_double)]
 
 
+class BatchedResult(C.Structure):
+    """lsq_batched_result: caller-owned host arrays of length B (trace: trace_cap * B, trace_x: trace_cap * n)."""
+    _fields_ = [("ssr", c_dp), ("ssr0", c_dp), ("iterations", c_ip),
+                ("converged", c_ip), ("x_converged", c_ip), ("f_converged", c_ip), ("g_converged", c_ip),
+                ("f_calls", c_ip), ("g_calls", c_ip), ("mul_calls", c_ip), ("status", c_ip), ("info", c_ip),
+                ("outer_iterations", C.c_int), ("seconds", C.c_double), ("trace_cap", C.c_int),
+                ("trace_ssr", c_dp), ("trace_gnorm", c_dp), ("trace_delta", c_dp), ("trace_rho", c_dp),
+                ("trace_accept", c_ip), ("trace_x", c_dp)]
+
+
 def build(verbose=False):
     """Compile liblsqhip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     cmd = ["make", "-C", os.path.join(_HERE, "csrc"), "-j8"]
@@ -156,6 +166,8 @@ def lib():
         "lsq_options_default": (None, [C.POINTER(Options)]),
         "lsq_optimize": (i, [vp, i, i, vp, vp, vp, F_CALLBACK, G_CALLBACK, vp, C.POINTER(Options),
                              C.POINTER(Result)]),
+        "lsq_optimize_batched": (i, [vp, i, i, vp, vp, vp, F_CALLBACK, G_CALLBACK, vp, C.POINTER(Options),
+                                     C.POINTER(BatchedResult)]),
         "lsq_model_tanh_create": (i, [vp, vp, c_dp, c_dp, pvp]),
         "lsq_model_destroy": (i, [vp]),
         "lsq_model_f": (F_CALLBACK, []),

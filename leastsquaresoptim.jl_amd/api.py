@@ -783,6 +783,91 @@ def converged(r):
     return r.x_converged or r.f_converged or r.g_converged
 
 
+class _HostCallbacks:
+    """f! / g! of a host-side problem as the C callbacks of lsq_optimize / lsq_optimize_batched (device pointers in, numpy out).
+    Host-side g!: the Jacobian values live in PAGE-LOCKED memory for the duration of the solve -- g! writes them there
+    directly (a sparse J gets its .data rebound to the pinned array, a dense J is handed over as a pinned column-major
+    view) and the upload after every g!(J, x) is asynchronous (lsq_mat_set_values_async): no staging copy, no blocked
+    host, PCIe rate instead of the pageable-copy rate.  SURVEY 8f-1; levenberg_marquardt.jl:77-81 is where the upload sits.
+    bind() rebinds, release() (in a finally) hands J.data back in ordinary memory; exceptions raised inside f! / g! are
+    collected in .err and surfaced by the caller after the C call has returned."""
+
+    def __init__(self, ctx, nls, Jd, stage=None):
+        self.ctx, self.nls, self.Jd = ctx, nls, Jd
+        self.n, self.m = len(nls.x), len(nls.y)
+        self.is_op = isinstance(nls.J, DeviceOperator)
+        self.own_stage = stage is None
+        self.given_stage = stage
+        self.stage = None
+        self.J_user = nls.J
+        self.data_user = None
+        self.J_for_g = None
+        self.err = []
+        self.xh, self.yh = np.zeros(self.n), np.zeros(self.m)
+        self.F, self.G = _lib.F_CALLBACK(self._fcb), _lib.G_CALLBACK(self._gcb)
+
+    def bind(self):
+        # (called inside the caller's try: whatever happens after the rebinding, release() hands J.data back)
+        if self.is_op:
+            return
+        nls, Jd = self.nls, self.Jd
+        self.stage = self.given_stage if self.given_stage is not None else PinnedBuffer(self.ctx, Jd.nnz)
+        if Jd.sparse:
+            self.data_user = nls.J.data
+            np.copyto(self.stage.array, self.data_user)
+            nls.J.data = self.stage.array
+            self.J_for_g = nls.J
+        else:
+            self.J_for_g = self.stage.array.reshape((self.m, self.n), order="F")
+            np.copyto(self.J_for_g, nls.J)
+
+    def _fcb(self, d_out, d_x, _):
+        L = lib()
+        try:
+            check(L.lsq_d2h(self.ctx.h, self.xh.ctypes.data_as(C.c_void_p), d_x, self.n * 8))
+            self.nls.f_(self.yh, self.xh)
+            check(L.lsq_h2d(self.ctx.h, d_out, self.yh.ctypes.data_as(C.c_void_p), self.m * 8))
+            return 0
+        except Exception as e:  # surfaced after the C call returns
+            self.err.append(e)
+            return 1
+
+    def _gcb(self, Jh, d_x, _):
+        L = lib()
+        nls, Jd, stage = self.nls, self.Jd, self.stage
+        try:
+            check(L.lsq_d2h(self.ctx.h, self.xh.ctypes.data_as(C.c_void_p), d_x, self.n * 8))
+            if self.is_op:   # g! updates the operator's own state; nothing to upload
+                nls.g_(nls.J, self.xh)
+                return 0
+            Jd.upload_wait()            # (the previous upload has long finished; g! is about to overwrite its source)
+            nls.g_(self.J_for_g, self.xh)
+            if Jd.sparse and nls.J.data is not stage.array:     # g! replaced J.data instead of writing into it
+                np.copyto(stage.array, nls.J.data)
+                nls.J.data = stage.array
+            Jd.set_values_async(stage)
+            return 0
+        except Exception as e:
+            self.err.append(e)
+            return 1
+
+    def release(self):
+        stage = self.stage
+        if stage is None:
+            return
+        # hand the values back in ordinary memory before the pinned buffer can go away
+        self.Jd.upload_wait()
+        if self.Jd.sparse:
+            if self.data_user is not None:
+                self.data_user[:] = stage.array
+                self.nls.J.data = self.data_user
+        elif self.J_for_g is not None:
+            np.copyto(self.J_user, self.J_for_g)
+        if self.own_stage:
+            stage.free()
+        self.stage = None
+
+
 def _run_native(ctx, optimizer_kind, solver_kind, Jd, dx, dy, fcb, gcb, user, x_tol, f_tol, g_tol,
                 iterations, delta, lower, upper, trace, n, allreduce=None, preconditioner=None, row_allreduce=None,
                 row_allreduce_user=None, global_rows=0, general_preconditioner=None):
@@ -875,64 +960,13 @@ def optimize_(nls, optimizer=None, x_tol=1e-8, f_tol=1e-8, g_tol=1e-8, iteration
     else:
         Jd = nls.J if is_op else DeviceMatrix(ctx, nls.J)
         dx, dy = DeviceVector(ctx, n, nls.x), DeviceVector(ctx, m, nls.y)
-    L = lib()
-    xh, yh = np.zeros(n), np.zeros(m)
-    err = []
-    # Host-side g!: the Jacobian values live in PAGE-LOCKED memory for the duration of the solve -- g! writes them there
-    # directly (a sparse J gets its .data rebound to the pinned array, a dense J is handed over as a pinned column-major
-    # view) and the upload after every g!(J, x) is asynchronous (lsq_mat_set_values_async): no staging copy, no blocked
-    # host, PCIe rate instead of the pageable-copy rate.  SURVEY 8f-1; levenberg_marquardt.jl:77-81 is where the upload sits.
-    stage = None
-    J_user = nls.J
-    data_user = None
-    J_for_g = None
-
-    def bind_stage():
-        # (called inside the try below: whatever happens after the rebinding, the finally hands J.data back)
-        nonlocal stage, data_user, J_for_g
-        stage = allocated._stage if allocated is not None and allocated._stage is not None else PinnedBuffer(ctx, Jd.nnz)
-        if Jd.sparse:
-            data_user = nls.J.data
-            np.copyto(stage.array, data_user)
-            nls.J.data = stage.array
-            J_for_g = nls.J
-        else:
-            J_for_g = stage.array.reshape((m, n), order="F")
-            np.copyto(J_for_g, nls.J)
-
-    def fcb(d_out, d_x, _):
-        try:
-            check(L.lsq_d2h(ctx.h, xh.ctypes.data_as(C.c_void_p), d_x, n * 8))
-            nls.f_(yh, xh)
-            check(L.lsq_h2d(ctx.h, d_out, yh.ctypes.data_as(C.c_void_p), m * 8))
-            return 0
-        except Exception as e:  # surfaced after the C call returns
-            err.append(e)
-            return 1
-
-    def gcb(Jh, d_x, _):
-        try:
-            check(L.lsq_d2h(ctx.h, xh.ctypes.data_as(C.c_void_p), d_x, n * 8))
-            if is_op:   # g! updates the operator's own state; nothing to upload
-                nls.g_(nls.J, xh)
-                return 0
-            Jd.upload_wait()            # (the previous upload has long finished; g! is about to overwrite its source)
-            nls.g_(J_for_g, xh)
-            if Jd.sparse and nls.J.data is not stage.array:     # g! replaced J.data instead of writing into it
-                np.copyto(stage.array, nls.J.data)
-                nls.J.data = stage.array
-            Jd.set_values_async(stage)
-            return 0
-        except Exception as e:
-            err.append(e)
-            return 1
-
-    F, G = _lib.F_CALLBACK(fcb), _lib.G_CALLBACK(gcb)
+    host = _HostCallbacks(ctx, nls, Jd, allocated._stage if allocated is not None else None)
+    err = host.err
+    F, G = host.F, host.G
     tracing = store_trace or show_trace or full_trace
     st = res = tr = None
     try:
-        if not is_op:
-            bind_stage()
+        host.bind()
         pc = gpc = None
         if getattr(solver, "P", None) is not None:
             gpc = _general_precond_trampolines(solver, ctx, Jd)
@@ -947,16 +981,7 @@ def optimize_(nls, optimizer=None, x_tol=1e-8, f_tol=1e-8, g_tol=1e-8, iteration
                                   row_allreduce_user=row_allreduce.user if row_allreduce is not None else None,
                                   global_rows=global_rows)
     finally:
-        if stage is not None:       # hand the values back in ordinary memory before the pinned buffer can go away
-            Jd.upload_wait()
-            if Jd.sparse:
-                if data_user is not None:
-                    data_user[:] = stage.array
-                    nls.J.data = data_user
-            elif J_for_g is not None:
-                np.copyto(J_user, J_for_g)
-            if allocated is None or allocated._stage is None:
-                stage.free()
+        host.release()
         if st is not None:
             # optimize! mutates nls.x / nls.y in place (levenberg_marquardt.jl:46): when an iteration throws
             # (RankDeficientException, IsFiniteException, ...) they hold that iteration's iterate, as in the reference
@@ -996,6 +1021,160 @@ def optimize_(nls, optimizer=None, x_tol=1e-8, f_tol=1e-8, g_tol=1e-8, iteration
     r.tr = states if store_trace else []
     if not is_op and allocated is None:
         Jd.free()
+    return r
+
+
+# ------------------------------------------------------------------------------------------------
+# B independent fits on a block-diagonal Jacobian: one trust region per block (lsq_optimize_batched)
+# ------------------------------------------------------------------------------------------------
+_BATCHED_INT = ("iterations", "converged", "x_converged", "f_converged", "g_converged", "f_calls", "g_calls", "mul_calls",
+                "status", "info")
+
+
+class BatchedResult:
+    """Result of optimize_batched_: arrays of length B named as the fields of LeastSquaresResult (ssr, iterations, converged,
+    x_converged, f_converged, g_converged, f_calls, g_calls, mul_calls), plus `status` / `info` (the lsq_status of each fit and
+    its block-local column / rank / index, -1 when there is none), `ssr0`, the stacked `minimizer`, `outer_iterations`,
+    `seconds` and, when requested, `trace` (ssr / gnorm / delta / rho / accept: (cap, B); x: (cap, n); row k of block b is only
+    meaningful for k < iterations[b]).  block(b) is fit b as a LeastSquaresResult."""
+
+    def __init__(self, nblocks, mb, nb, optimizer="LevenbergMarquardt", x_tol=1e-8, f_tol=1e-8, g_tol=1e-8):
+        self.nblocks, self.mb, self.nb = int(nblocks), int(mb), int(nb)
+        self.optimizer = optimizer
+        self.x_tol, self.f_tol, self.g_tol = float(x_tol), float(f_tol), float(g_tol)
+        B = self.nblocks
+        self.ssr, self.ssr0 = np.zeros(B), np.zeros(B)
+        for k in _BATCHED_INT:
+            setattr(self, k, np.zeros(B, dtype=np.int32))
+        self.info[:] = -1
+        self.minimizer = np.zeros(B * self.nb)
+        self.outer_iterations, self.seconds = 0, 0.0
+        self.trace = None
+
+    def block(self, b):
+        if not 0 <= b < self.nblocks:
+            raise IndexError("block %d of %d" % (b, self.nblocks))
+        r = LeastSquaresResult()
+        r.optimizer = self.optimizer
+        r.minimizer = self.minimizer[b * self.nb:(b + 1) * self.nb]
+        r.ssr, r.ssr0 = float(self.ssr[b]), float(self.ssr0[b])
+        r.iterations = int(self.iterations[b])
+        r.converged = bool(self.converged[b])
+        r.x_converged, r.f_converged, r.g_converged = bool(self.x_converged[b]), bool(self.f_converged[b]), bool(self.g_converged[b])
+        r.x_tol, r.f_tol, r.g_tol = self.x_tol, self.f_tol, self.g_tol
+        r.f_calls, r.g_calls, r.mul_calls = int(self.f_calls[b]), int(self.g_calls[b]), int(self.mul_calls[b])
+        r.status, r.info = int(self.status[b]), int(self.info[b])
+        r.trace = None
+        if self.trace is not None:
+            k = min(r.iterations, self.trace["ssr"].shape[0])
+            r.trace = {key: self.trace[key][:k, b].copy() for key in ("ssr", "gnorm", "delta", "rho", "accept")}
+            r.trace["x"] = self.trace["x"][:k, b * self.nb:(b + 1) * self.nb].copy()
+            # solves per iteration: Cholesky() is one, and Dogleg reuses its steps after a refused one (dogleg.jl:81)
+            inner = np.ones(k, dtype=np.int32)
+            if self.optimizer == "Dogleg" and k > 1:
+                inner[1:] = r.trace["accept"][:k - 1]
+            r.trace["inner"] = inner
+        return r
+
+
+def _batched_arguments(J, optimizer, n, lower, upper):
+    """Everything optimize_batched_ can refuse before a device call; returns (optimizer, solver)."""
+    if not _is_blockdiag(J):
+        raise ArgumentError(_lib.EARG, "optimize_batched_ needs a BlockDiagonal Jacobian: one trust region per block "
+                                       "needs the block shape")
+    if optimizer is None:
+        optimizer = LevenbergMarquardt(Cholesky())
+    solver = optimizer.solver if optimizer.solver is not None else Cholesky()
+    if isinstance(solver, QR):
+        raise ArgumentError(_lib.EARG, "solver QR() is not available for sparse Jacobians. "
+                                       "Choose between Cholesky() and LSMR()")
+    if isinstance(solver, LSMR):
+        raise ArgumentError(_lib.EARG, "optimize_batched_: LSMR() is not available per block (an iterative solve per block "
+                                       "is a different loop). Use Cholesky(), or optimize_ for one trust region over the "
+                                       "stacked problem")
+    if J.nb > 64:
+        raise ArgumentError(_lib.EARG, "optimize_batched_: Cholesky() per block needs blocks of at most 64 columns "
+                                       "(got nb = %d)" % J.nb)
+    for bound in (lower, upper):
+        if bound is not None and len(bound) and len(bound) != n:
+            raise ArgumentError(_lib.EARG, "Bounds must either be empty or of the same length as "
+                                           "the number of parameters.")
+    return default_optimizer(optimizer, solver), solver
+
+
+def _run_native_batched(ctx, optimizer_kind, solver_kind, Jh, shape, dx, dy, fcb, gcb, user, x_tol, f_tol, g_tol, iterations,
+                        delta, lower, upper, trace, optimizer_name, options_hook=None):
+    """lsq_optimize_batched on device buffers; returns (status, BatchedResult without its minimizer)."""
+    L = lib()
+    B, mb, nb = shape
+    n = B * nb
+    opt = _lib.Options()
+    L.lsq_options_default(C.byref(opt))
+    opt.x_tol, opt.f_tol, opt.g_tol = float(x_tol), float(f_tol), float(g_tol)
+    opt.iterations = int(iterations)
+    opt.delta = float(delta) if delta is not None else -1.0
+    keep = []
+    for name, bound in (("h_lower", lower), ("h_upper", upper)):
+        if bound is not None and len(bound):
+            v = np.ascontiguousarray(bound, dtype=np.float64)
+            setattr(opt, name, v.ctypes.data_as(_lib.c_dp))
+            keep.append(v)
+    if options_hook is not None:
+        options_hook(opt)
+    r = BatchedResult(B, mb, nb, optimizer_name, x_tol, f_tol, g_tol)
+    res = _lib.BatchedResult()
+    res.ssr, res.ssr0 = r.ssr.ctypes.data_as(_lib.c_dp), r.ssr0.ctypes.data_as(_lib.c_dp)
+    for k in _BATCHED_INT:
+        setattr(res, k, getattr(r, k).ctypes.data_as(_lib.c_ip))
+    tr = None
+    if trace:
+        cap = int(iterations)
+        tr = dict(ssr=np.zeros((cap, B)), gnorm=np.zeros((cap, B)), delta=np.zeros((cap, B)), rho=np.zeros((cap, B)),
+                  accept=np.zeros((cap, B), dtype=np.int32), x=np.zeros((cap, n)))
+        res.trace_cap = cap
+        for key in ("ssr", "gnorm", "delta", "rho", "x"):
+            setattr(res, "trace_" + key, tr[key].ctypes.data_as(_lib.c_dp))
+        res.trace_accept = tr["accept"].ctypes.data_as(_lib.c_ip)
+    st = L.lsq_optimize_batched(ctx.h, optimizer_kind, solver_kind, Jh, dx.ptr, dy.ptr, fcb, gcb, user, C.byref(opt),
+                                C.byref(res))
+    r.outer_iterations, r.seconds = int(res.outer_iterations), float(res.seconds)
+    if tr is not None:
+        k = r.outer_iterations
+        r.trace = {key: v[:k].copy() for key, v in tr.items()}
+    return st, r
+
+
+def optimize_batched_(nls, optimizer=None, x_tol=1e-8, f_tol=1e-8, g_tol=1e-8, iterations=1000, delta=None,
+                      lower=(), upper=(), ctx=None, full_trace=False):
+    """B runs of optimize! in one device loop: nls.J is a BlockDiagonal(B, mb, nb) and fit b is the problem made of residual
+    rows b*mb .. and parameters b*nb .. -- its own trust region, accept decisions, convergence test and counts
+    (levenberg_marquardt.jl:39-144 / dogleg.jl:41-203 per block; include/lsqhip.h: lsq_optimize_batched).  f_ / g_ have the
+    signatures optimize_ uses and see the stacked x, y, J.data; they must be block-separable and deterministic.  Default
+    optimizer: LevenbergMarquardt(Cholesky()).  A fit that fails (status[b] != 0) does not end the call.  Mutates nls.x,
+    nls.y, nls.J; returns a BatchedResult."""
+    n, m = len(nls.x), len(nls.y)
+    optimizer, solver = _batched_arguments(nls.J, optimizer, n, lower, upper)
+    ctx = ctx or default_context()
+    J = nls.J
+    Jd = DeviceMatrix(ctx, J)
+    dx, dy = DeviceVector(ctx, n, nls.x), DeviceVector(ctx, m, nls.y)
+    host = _HostCallbacks(ctx, nls, Jd)
+    st = r = None
+    try:
+        host.bind()
+        st, r = _run_native_batched(ctx, optimizer.kind, solver.kind, Jd.h, (J.nblocks, J.mb, J.nb), dx, dy, host.F, host.G,
+                                    None, x_tol, f_tol, g_tol, iterations, delta, lower, upper, full_trace, optimizer.name)
+    finally:
+        host.release()
+        if st is not None:
+            nls.x[:] = dx.get()
+            nls.y[:] = dy.get()
+    if host.err:
+        raise host.err[0]
+    check(st)
+    r.minimizer = nls.x
+    r.jacobian = nls.J
+    Jd.free()
     return r
 
 

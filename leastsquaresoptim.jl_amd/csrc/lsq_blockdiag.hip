@@ -29,6 +29,7 @@
 constexpr int BD_R = 32;           // rows per streamed chunk
 constexpr int BD_CS = BD_R + 2;    // column stride of the staged chunk (doubles)
 constexpr int BD_MISC = 104;       // doubles behind M and W: y chunk (32) | right-hand side (64) | scalars (8)
+constexpr double BD_MIN_DIAGONAL = 1e-6, BD_MAX_DIAGONAL = 1e32;   // levenberg_marquardt.jl:85 (per-block damping, `delta`)
 
 // doubles of LDS per block (= per group of G wavefronts)
 static inline size_t bd_group_doubles(int nb) { return 2 * (size_t)(16 * ((nb + 15) / 16)) * S64_LS + BD_MISC; }
@@ -40,7 +41,18 @@ __global__ void k_bd_init(int *info) {
 template <int G, bool PIVOT>
 __global__ void __launch_bounds__(256)
 k_bd_solve(int B, int mb, int nb, const double *__restrict__ vals, const double *__restrict__ scale,
-           const double *__restrict__ y, const double *__restrict__ damp, double *__restrict__ x, int *__restrict__ info) {
+           const double *__restrict__ y, const double *__restrict__ damp, double *__restrict__ x, int *__restrict__ info,
+           const int *__restrict__ active, int *__restrict__ binfo, double *__restrict__ r_out,
+           double *__restrict__ diag_out, const double *__restrict__ delta) {
+    // The last five are the batched trust-region loop's (lsq_batched.hip); all null = lsq_blockdiag_solve, unchanged:
+    //   active    per-block mask: a workgroup none of whose blocks is active returns before loading anything; an inactive
+    //             block that shares its workgroup with active ones (G = 1) runs as padding (no loads, no stores)
+    //   binfo     per-block verdict INSTEAD of the cross-block words of `info`: 0, or LM: the 1-based column at which the block's
+    //             dpotrf stops / Dogleg: nb - rank_b
+    //   r_out     r_b = J_b'y_b (the gradient of levenberg_marquardt.jl:102 / dogleg.jl:99 when y = fcur)
+    //   diag_out  diag(J_b'J_b) = colsumabs2(J_b) (levenberg_marquardt.jl:82 / dogleg.jl:85) before any damping
+    //   delta     LM with one trust region per block (damp == nullptr): the damping of levenberg_marquardt.jl:84-86 is formed
+    //             here from the block's own diagonal -- clamp(dtd_b, MIN * mean(dtd_b), MAX * mean(dtd_b)) * (1 / delta_b)
     extern __shared__ double bd_lds[];
     constexpr int GT = 64 * G;                 // threads per block of the matrix
     constexpr int TPW = G == 4 ? 3 : 1;        // upper tiles per wavefront (10 tiles over 4 wavefronts / 1 tile)
@@ -49,7 +61,15 @@ k_bd_solve(int B, int mb, int nb, const double *__restrict__ vals, const double 
     const int wg = G == 4 ? __builtin_amdgcn_readfirstlane(wv) : 0;      // wavefront inside its group
     const int gt = G == 4 ? tid : lane;                                  // thread inside its group
     const int b = G == 4 ? (int)blockIdx.x : (int)blockIdx.x * 4 + wv;
-    const bool live = b < B;
+    if (active) {
+        bool any = false;
+        for (int q = 0; q < (G == 4 ? 1 : 4); ++q) {
+            const int bq = G == 4 ? (int)blockIdx.x : (int)blockIdx.x * 4 + q;
+            any = any || (bq < B && active[bq] != 0);
+        }
+        if (!any) return;              // (the same answer in every thread of the workgroup)
+    }
+    const bool live = b < B && (!active || active[b] != 0);
     const int NT = (nb + 15) >> 4, ncp = 16 * NT;
     const int msz = ncp * S64_LS;
     double *M = bd_lds + (G == 4 ? 0 : wv) * (size_t)(2 * msz + BD_MISC);
@@ -143,13 +163,29 @@ k_bd_solve(int B, int mb, int nb, const double *__restrict__ vals, const double 
         for (int r = 0; r < 4; ++r) {
             const int i = 16 * wg + kq + 4 * r;
             rv[i] = racc[r] * sc(i);
+            if (r_out && live && i < nb) r_out[(size_t)b * nb + i] = rv[i];
         }
     }
     if (gt == 0) misc_i[1] = 0;
     __syncthreads();
+    double dsum = 0.0;
+    if (delta) {                       // sum(dtd_b) in index order, every thread its own copy (LDS broadcast reads)
+        for (int k = 0; k < nb; ++k) dsum += M[k * S64_LS + k];
+        __syncthreads();
+    }
     if (gt < ncp) {
         if (!live || gt >= nb) M[gt * S64_LS + gt] = 1.0;                          // padding: identity
-        else if (damp) M[gt * S64_LS + gt] += damp[(size_t)b * nb + gt];
+        else {
+            const double d = M[gt * S64_LS + gt];
+            if (diag_out) diag_out[(size_t)b * nb + gt] = d;
+            if (damp) M[gt * S64_LS + gt] = d + damp[(size_t)b * nb + gt];
+            else if (delta) {
+                const double mean = dsum / nb;
+                const double lo = BD_MIN_DIAGONAL * mean, hi = BD_MAX_DIAGONAL * mean;
+                const double dc = d > hi ? hi : (d < lo ? lo : d);
+                M[gt * S64_LS + gt] = d + dc * (1.0 / delta[b]);
+            }
+        }
     }
     __syncthreads();
 
@@ -182,8 +218,9 @@ k_bd_solve(int B, int mb, int nb, const double *__restrict__ vals, const double 
         }
         const int fail = misc_i[1];
         if (wg == 0 && live) {
+            if (binfo && lane == 0) binfo[b] = fail;
             if (fail) {
-                if (lane == 0) {
+                if (lane == 0 && !binfo) {
                     atomicMin(&info[0], b * nb + fail);
                     atomicMin(&info[1], b);
                 }
@@ -269,8 +306,9 @@ k_bd_solve(int B, int mb, int nb, const double *__restrict__ vals, const double 
             __syncthreads();
         }
         if (wg == 0 && live) {
+            if (binfo && lane == 0) binfo[b] = dead ? nb - rank : 0;
             if (dead) {
-                if (lane == 0) {
+                if (lane == 0 && !binfo) {
                     atomicMin(&info[1], b);
                     atomicAdd(&info[2], nb - rank);
                 }
@@ -352,17 +390,37 @@ int lsq_blockdiag_solver_alloc(lsq_solver *s, const lsq_mat *J) {
     return LSQ_OK;
 }
 
+struct BdExtra {       // the batched loop's operands of k_bd_solve (all null: the plain solve)
+    const int *active = nullptr;
+    int *binfo = nullptr;
+    double *r_out = nullptr, *diag_out = nullptr;
+    const double *delta = nullptr;
+};
+
 template <int G, bool PIVOT>
-static int bd_launch(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x) {
-    lsq_ctx *c = s->ctx;
-    const int B = s->bd_blocks;
-    const size_t lds = (G == 4 ? 1 : 4) * bd_group_doubles(s->bd_nb) * sizeof(double);
+static int bd_launch(lsq_ctx *c, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *d_info, const BdExtra &e) {
+    const int B = J->bd_blocks;
+    const size_t lds = (G == 4 ? 1 : 4) * bd_group_doubles(J->bd_nb) * sizeof(double);
     LSQ_TRY(lsq_set_lds(c, (const void *)k_bd_solve<G, PIVOT>, lds));
     const int grid = G == 4 ? B : (B + 3) / 4;
-    LSQ_LAUNCH((k_bd_solve<G, PIVOT>), dim3(grid), dim3(256), lds, c->stream, B, s->bd_mb, s->bd_nb,
-               (const double *)J->csc.d_val, J->d_colscale, d_y, d_damp, d_x, s->d_info);
+    LSQ_LAUNCH((k_bd_solve<G, PIVOT>), dim3(grid), dim3(256), lds, c->stream, B, J->bd_mb, J->bd_nb,
+               (const double *)J->csc.d_val, J->d_colscale, d_y, d_damp, d_x, d_info, e.active, e.binfo, e.r_out, e.diag_out,
+               e.delta);
     LSQ_HIP(hipGetLastError());
     return LSQ_OK;
+}
+
+// One batched solve for the per-block trust-region loop (lsq_batched.hip): pivot = false: LM, damping formed in the kernel
+// from d_delta (B trust-region radii); pivot = true: Dogleg's Gauss-Newton step.  Only blocks with d_active[b] != 0 are
+// solved (x_b, r_b, diag_b, binfo[b] of the others are left alone).  Nothing is read back.
+int lsq_blockdiag_solve_blocks(lsq_ctx *c, lsq_mat *J, bool pivot, const double *d_y, const double *d_delta, double *d_x,
+                               const int *d_active, int *d_binfo, double *d_r, double *d_diag) {
+    LSQ_TRY(lsq_ensure_csc(J));
+    BdExtra e;
+    e.active = d_active; e.binfo = d_binfo; e.r_out = d_r; e.diag_out = d_diag; e.delta = pivot ? nullptr : d_delta;
+    const bool wide = J->bd_nb > 16;
+    if (pivot) return wide ? bd_launch<4, true>(c, J, d_y, nullptr, d_x, nullptr, e) : bd_launch<1, true>(c, J, d_y, nullptr, d_x, nullptr, e);
+    return wide ? bd_launch<4, false>(c, J, d_y, nullptr, d_x, nullptr, e) : bd_launch<1, false>(c, J, d_y, nullptr, d_x, nullptr, e);
 }
 
 // dense_cholesky.jl:29-35 (d_damp == nullptr: pivoted, Dogleg) and :43-59 (damped, unpivoted, LM) on the stacked system
@@ -377,8 +435,9 @@ int lsq_blockdiag_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const doub
     LSQ_TRY(lsq_ensure_csc(J));        // (a device-side g! may have written the product mirrors only)
     LSQ_LAUNCH(k_bd_init, dim3(1), dim3(64), 0, c->stream, s->d_info);
     const bool wide = s->bd_nb > 16;
-    if (d_damp) LSQ_TRY(wide ? (bd_launch<4, false>(s, J, d_y, d_damp, d_x)) : (bd_launch<1, false>(s, J, d_y, d_damp, d_x)));
-    else LSQ_TRY(wide ? (bd_launch<4, true>(s, J, d_y, d_damp, d_x)) : (bd_launch<1, true>(s, J, d_y, d_damp, d_x)));
+    const BdExtra none;
+    if (d_damp) LSQ_TRY(wide ? (bd_launch<4, false>(c, J, d_y, d_damp, d_x, s->d_info, none)) : (bd_launch<1, false>(c, J, d_y, d_damp, d_x, s->d_info, none)));
+    else LSQ_TRY(wide ? (bd_launch<4, true>(c, J, d_y, d_damp, d_x, s->d_info, none)) : (bd_launch<1, true>(c, J, d_y, d_damp, d_x, s->d_info, none)));
     s->last_bd_path = d_damp ? 1 : 2;
     s->last_bd_block = -1;
     int st4[4] = {0, 0, 0, 0};

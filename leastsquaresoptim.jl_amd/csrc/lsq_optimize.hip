@@ -689,6 +689,7 @@ static int call_g(lsq_g_callback g, lsq_mat *J, const double *x, void *user) {
     CB(g(J, x, user));
     return lsq_ensure_csr(J);
 }
+int lsq_call_g(lsq_g_callback g, lsq_mat *J, const double *x, void *user) { return call_g(g, J, x, user); }
 
 // ---------------------------------------------------------------------------------------------
 // levenberg_marquardt.jl:39-144

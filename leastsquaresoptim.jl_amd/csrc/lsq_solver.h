@@ -231,3 +231,7 @@ int lsq_qr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_d
 // implemented in lsq_blockdiag.hip
 int lsq_blockdiag_solver_alloc(lsq_solver *s, const lsq_mat *J);
 int lsq_blockdiag_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);
+int lsq_blockdiag_solve_blocks(lsq_ctx *c, lsq_mat *J, bool pivot, const double *d_y, const double *d_delta, double *d_x,
+                               const int *d_active, int *d_binfo, double *d_r, double *d_diag);
+// implemented in lsq_optimize.hip: g!(J, x) with the handle's bookkeeping around it (version, mirrors)
+int lsq_call_g(lsq_g_callback g, lsq_mat *J, const double *x, void *user);

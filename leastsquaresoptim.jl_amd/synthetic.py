@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from .api import (DeviceVector, LeastSquaresResult, _run_native, default_context)
+from .api import (DeviceVector, LeastSquaresResult, _run_native, _run_native_batched, default_context)
 
 BASE_SEED = 20260928
 
@@ -155,6 +155,24 @@ class TanhProblem:
         r.f_calls, r.g_calls, r.mul_calls = res.f_calls, res.g_calls, res.mul_calls
         r.seconds, r.lsmr_iterations = res.seconds, int(res.lsmr_iterations)
         r.trace = tr
+        r.minimizer = self.x.get() if fetch_x else None
+        return r
+
+    def optimize_batched(self, optimizer_kind=_lib.LEVENBERG_MARQUARDT, solver_kind=_lib.CHOLESKY, x_tol=1e-8, f_tol=1e-8,
+                         g_tol=1e-8, iterations=1000, delta=None, lower=None, upper=None, trace=False, fetch_x=True):
+        """The twin of optimize() on a blockdiag= problem: one trust region per block (lsq_optimize_batched), f! / g! on the
+        device, no host callbacks.  Returns an api.BatchedResult."""
+        if self.blockdiag is None:
+            raise _lib.ArgumentError(_lib.EARG, "optimize_batched needs a problem built with blockdiag=(nblocks, mb, nb)")
+        if self._fg is None:
+            L = lib()
+            self._Jd = _Handle(self.J)
+            self._fg = (L.lsq_model_f(), L.lsq_model_g())
+        name = "LevenbergMarquardt" if optimizer_kind == _lib.LEVENBERG_MARQUARDT else "Dogleg"
+        st, r = _run_native_batched(self.ctx, optimizer_kind, solver_kind, self.J, self.blockdiag, self.x, self.fcur,
+                                    self._fg[0], self._fg[1], self.model, x_tol, f_tol, g_tol, iterations, delta, lower, upper,
+                                    trace, name)
+        check(st)
         r.minimizer = self.x.get() if fetch_x else None
         return r
 

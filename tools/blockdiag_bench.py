@@ -8,6 +8,13 @@
     python tools/blockdiag_bench.py lm         LM(Cholesky()) on the block handle vs LM(LSMR()) on a plain CSC handle of the
                                                same matrix (B=8192, mb=256, nb=32): seconds per outer iteration, to convergence
     python tools/blockdiag_bench.py all
+    python tools/blockdiag_bench.py lm --batched   one trust region per block (lsq_optimize_batched) against the stacked loop on
+                                               the heterogeneous tanh problem (block b starts from 0.3 (b mod 4) (+1, -1, ..),
+                                               0.1 N(0,1) added to the right-hand side of blocks b mod 8 == 5), device model,
+                                               B=4096 with 256 x 16 and 128 x 32 blocks: seconds to convergence of each loop
+                                               by its own criterion (stacked: the summed one; batched: every block) and
+                                               seconds per outer iteration over 10 iterations with zero tolerances (every
+                                               block active in both loops)
 
 Every solve is timed with HIP events on the library's stream (hipEventRecord through ctypes) around the whole lsq_ldiv_damped
 call -- it ends with the status hand-over to the host, so event time and wall time agree to a few microseconds; both are
@@ -135,12 +142,56 @@ def bench_lm(ctx, reps):
     pl.close()
 
 
+def bench_batched(ctx, reps):
+    LM, CH = lsq._lib.LEVENBERG_MARQUARDT, lsq._lib.CHOLESKY
+    for B, mb, nb in ((4096, 256, 16), (4096, 128, 32)):
+        m, n = B * mb, B * nb
+        A = lsq.synthetic.blockdiag_inputs(B, mb, nb, 4)
+        A3 = A.reshape((B, nb, mb))
+        _, b = lsq.synthetic.rhs_for(lambda t: np.einsum("bjr,bj->br", A3, t.reshape((B, nb))).reshape(-1), m, n, 4)
+        noisy = np.repeat(np.arange(B) % 8 == 5, mb)
+        b[noisy] += 0.1 * lsq.synthetic.normal(m, 4 + 303)[noisy]
+        x0 = (0.3 * np.repeat(np.arange(B) % 4, nb) * np.tile(np.where(np.arange(nb) % 2 == 0, 1.0, -1.0), B)).astype(np.float64)
+        pr = lsq.synthetic.TanhProblem(m, n, ctx=ctx, blockdiag=(B, mb, nb), inputs=A, b=b)
+        out = {"bench": "batched_vs_stacked", "B": B, "mb": mb, "nb": nb, "reps": reps}
+
+        def timed(fn):
+            runs = []
+            for k in range(2 + reps):
+                pr.reset(x0)
+                ctx.sync()
+                r = fn()
+                if k >= 2:
+                    runs.append(r)
+            sec = [r.seconds for r in runs]
+            return runs[-1], statistics.median(sec), min(sec), max(sec)
+
+        r, med, lo, hi = timed(lambda: pr.optimize_batched(LM, CH, iterations=200, fetch_x=False))
+        out["batched"] = {"all_converged": bool(np.all(r.converged == 1)), "outer_iterations": r.outer_iterations,
+                          "iterations_min": int(r.iterations.min()), "iterations_median": float(np.median(r.iterations)),
+                          "ssr": float(r.ssr.sum()), "seconds_median": med, "seconds_min": lo, "seconds_max": hi}
+        r, med, lo, hi = timed(lambda: pr.optimize(LM, CH, iterations=200, fetch_x=False))
+        out["stacked"] = {"converged": r.converged, "outer_iterations": r.iterations, "ssr": r.ssr, "seconds_median": med,
+                          "seconds_min": lo, "seconds_max": hi}
+        K = 10
+        r, med, lo, hi = timed(lambda: pr.optimize_batched(LM, CH, x_tol=0.0, f_tol=0.0, g_tol=0.0, iterations=K, fetch_x=False))
+        out["batched"]["us_per_outer_all_active"] = {"median": med / K * 1e6, "min": lo / K * 1e6, "max": hi / K * 1e6}
+        r, med, lo, hi = timed(lambda: pr.optimize(LM, CH, x_tol=0.0, f_tol=0.0, g_tol=0.0, iterations=K, fetch_x=False))
+        out["stacked"]["us_per_outer_all_active"] = {"median": med / K * 1e6, "min": lo / K * 1e6, "max": hi / K * 1e6}
+        print(json.dumps(out))
+        pr.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["dense", "roofline", "lm", "all"])
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--batched", action="store_true", help="the per-block trust-region loop against the stacked one (only this leg)")
     a = ap.parse_args()
     ctx = lsq.default_context()
+    if a.batched:
+        bench_batched(ctx, max(a.reps, 10))
+        return
     if a.what in ("dense", "all"):
         bench_dense(ctx, max(a.reps, 10))
     if a.what in ("roofline", "all"):
