@@ -37,7 +37,8 @@ typedef struct lsq_mat lsq_mat;       /* Jacobian: dense column-major or CSC (+C
 typedef struct lsq_solver lsq_solver; /* AbstractAllocatedSolver (types.jl:138-139) */
 typedef struct lsq_model lsq_model;   /* built-in device-side f!/g! (synthetic benchmarks) */
 
-typedef enum { LSQ_QR = 0, LSQ_CHOLESKY = 1, LSQ_LSMR = 2 } lsq_solver_kind;       /* types.jl:79-86 */
+/* types.jl:79-86; LSQ_BLOCK_QR: QR() per block of a block-diagonal handle (lsq_blockdiag_create), one rank decision per block */
+typedef enum { LSQ_QR = 0, LSQ_CHOLESKY = 1, LSQ_LSMR = 2, LSQ_BLOCK_QR = 3 } lsq_solver_kind;
 typedef enum { LSQ_DOGLEG = 0, LSQ_LEVENBERG_MARQUARDT = 1 } lsq_optimizer_kind;   /* types.jl:90-98 */
 
 const char *lsq_last_error(void);
@@ -71,7 +72,14 @@ int lsq_csc_create(lsq_ctx *ctx, int m, int n, const int *h_colptr, const int *h
  * lsq_solver_create accepts it with LSQ_CHOLESKY when nb <= 64 -- J'J + diag(damp) is block-diagonal, so the normal
  * equations of LevenbergMarquardt(Cholesky()) / Dogleg(Cholesky()) are B independent nb x nb factorisations, one pass over
  * the values per solve, with the reference's semantics on the stacked system (one trust region, LSQ_ENOTPD at the column
- * where the stacked dpotrf stops, LSQ_ERANK when the stacked pivoted factorisation stops early).  LSQ_QR stays refused. */
+ * where the stacked dpotrf stops, LSQ_ERANK when the stacked pivoted factorisation stops early).  LSQ_QR stays refused.
+ * LSQ_BLOCK_QR (nb <= 64; any other handle, or nb > 64: LSQ_EARG) is the backward-stable direct solver on such a handle:
+ * per block b the reference's QR() on that block alone (dense_qr.jl:30-88) -- x_b = ldiv!(qr!(J_b, ColumnNorm()), y_b) with
+ * xGELSY's rank decision at rcond = min(mb, nb) eps; damped: the same on [J_b; diag(sqrt(damp_b))] with right-hand side
+ * (y_b, 0) and rcond = nb eps.  The Gram matrix is never formed; a rank-deficient, an all-zero (x_b = 0) or a wide block
+ * (mb < nb) gets its minimum-norm solution and is never an error.  nmul is 1, damp is left as it is, a column-scaled handle
+ * means J_b S_b.  lsq_ldiv, lsq_ldiv_damped, lsq_optimize (one trust region over the stacked problem) and
+ * lsq_optimize_batched take it. */
 int lsq_blockdiag_create(lsq_ctx *ctx, int nblocks, int mb, int nb, lsq_mat **out);
 /* 0 blocks for any other handle */
 int lsq_mat_blockdiag_info(const lsq_mat *J, int *nblocks, int *mb, int *nb);
@@ -206,7 +214,7 @@ typedef int (*lsq_device_allreduce_callback)(double *d_buf, int count, void *hip
 /* row-sharded operator-level use (lsq_ldiv / lsq_ldiv_damped with LSMR on a row block J_p; y is the local slice, x the
  * replicated solution): installs the all-reduce hook of lsq_options.row_allreduce on this solver.  NULL removes it. */
 int lsq_solver_set_row_allreduce(lsq_solver *s, lsq_device_allreduce_callback cb, void *user, long long global_rows);
-/* diagnostics of the last solve: LSMR istop / iterations, QR numerical rank */
+/* diagnostics of the last solve: LSMR istop / iterations, QR numerical rank (LSQ_BLOCK_QR: the sum of the block ranks) */
 int lsq_solver_info(const lsq_solver *s, int *lsmr_iter, int *lsmr_istop, int *qr_rank);
 /* which factorisation the last QR solve used (dense_qr.jl:37,83 always runs geqp3; this build only needs the
  * pivoted sweep when the rank decision is open):  0 none yet, 1 one-stage pivoted Householder,
@@ -223,9 +231,12 @@ int lsq_solver_qr_panel(const lsq_solver *s, int *kind);
  * 4 like 2 with the whole factorisation in ONE launch (k_chol_tiles: one resident workgroup per 64 x 64 upper tile,
  * n <= 1408; repeated as 2 if one of its bounded waits gives up) */
 int lsq_solver_chol_path(const lsq_solver *s, int *path);
-/* diagnostics of the last block solve: which path (0 none yet, 1 batched unpivoted LM, 2 batched pivoted Dogleg) and,
- * after LSQ_ENOTPD / LSQ_ERANK, the block that decided it (else -1) */
+/* diagnostics of the last block solve: which path (0 none yet, 1 batched unpivoted LM, 2 batched pivoted Dogleg, 3 batched
+ * per-block pivoted QR: LSQ_BLOCK_QR, block = -1) and, after LSQ_ENOTPD / LSQ_ERANK, the block that decided it (else -1) */
 int lsq_solver_blockdiag_path(const lsq_solver *s, int *path, int *block);
+/* LSQ_BLOCK_QR: the numerical rank of every block in the last solve (h_ranks: nblocks ints; -1 before the first solve).
+ * LSQ_EARG for a solver of another kind. */
+int lsq_solver_blockdiag_ranks(const lsq_solver *s, int *h_ranks);
 
 /* The fast paths above that rely on co-resident workgroups (one-launch Cholesky, pipelined triangular solves, the QR panel's slab
  * exchange + pipelined certified solve) wait with a bound; a wait that gives up makes the solve repeat itself on the
@@ -326,6 +337,10 @@ int lsq_optimize(lsq_ctx *ctx, int optimizer, int solver_kind, lsq_mat *J, doubl
  * block at which dpotrf stops), LSQ_ERANK (Dogleg; info[b] = the rank of the block's pivoted factorisation) or LSQ_ENONFINITE
  * (check_isfinite, utils.jl:70-75; info[b] = the first non-finite index inside the block), it keeps the iterate it held and
  * the others go on; the call returns LSQ_OK.  Callback failures, HIP errors and bad arguments are call-level.
+ * With LSQ_BLOCK_QR the per-block solver is the reference's QR() (dense_qr.jl:30-88) instead: a block never fails on rank,
+ * status[b] stays LSQ_OK and info[b] is the numerical rank of the block's last solve (-1 only where nothing was solved) --
+ * under LevenbergMarquardt that is the rank of [J_b; diag(sqrt(damp_b))], nb for any positive damping, under Dogleg of J_b;
+ * LSQ_ENONFINITE is as above.
  * f and g are the callbacks of lsq_optimize on the stacked x (n), residual (m) and lsq_mat_values(J); they must be
  * block-separable (rows of block b depend on x_b only -- what a block-diagonal Jacobian says) and deterministic.  They are
  * called once per outer iteration for all blocks: g is handed, for every block that does not need a new Jacobian, the x_b at

@@ -28,7 +28,7 @@ PRECOND_UPDATE_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_
 PRECOND_LDIV_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)                # (d_out, d_in, user)
 
 OK, EDIM, ENOTPD, ERANK, ENONFINITE, EBOUNDS, EHIP, EARG, ECALLBACK, ERCCL = range(10)
-QR, CHOLESKY, LSMR = 0, 1, 2
+QR, CHOLESKY, LSMR, BLOCK_QR = 0, 1, 2, 3
 DOGLEG, LEVENBERG_MARQUARDT = 0, 1
 
 
@@ -157,6 +157,7 @@ def lib():
         "lsq_solver_qr_panel": (i, [vp, c_ip]),
         "lsq_solver_chol_path": (i, [vp, c_ip]),
         "lsq_solver_blockdiag_path": (i, [vp, c_ip, c_ip]),
+        "lsq_solver_blockdiag_ranks": (i, [vp, c_ip]),
         "lsq_solver_stats": (i, [vp, c_ip, c_ip]),
         "lsq_ctx_fallback_stats": (i, [vp, c_ip]),
         "lsq_ctx_device_info": (i, [vp, c_ip, c_ip, C.c_char_p, i]),

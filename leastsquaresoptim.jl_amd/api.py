@@ -37,6 +37,14 @@ class Cholesky(AbstractSolver):
     kind = _lib.CHOLESKY
 
 
+class BlockQR(AbstractSolver):
+    """QR() per block of a BlockDiagonal Jacobian (nb <= 64): column-pivoted QR of every block with its own rank decision
+    (dense_qr.jl:30-88 on J_b alone) -- backward stable where Cholesky() squares the condition number, and a rank-deficient,
+    all-zero or wide block gets its minimum-norm solution instead of an error.  QR() on the stacked matrix would make ONE
+    rank decision; this makes one per fit."""
+    kind = _lib.BLOCK_QR
+
+
 class LSMR(AbstractSolver):
     """LSMR(preconditioner!, P) (types.jl:82-86).
 
@@ -128,7 +136,8 @@ class BlockDiagonal:
     [block][column][row] -- B column-major mb x nb blocks back to back, which IS the nzval order of `.tocsc()`.
     On the device it becomes a CSC handle that knows its block shape (lsq_blockdiag_create): LSMR() is the default solver
     (types.jl:114-127: anything not dense), Cholesky() solves the B normal-equation blocks in one pass (nb <= 64),
-    QR() is refused as for every sparse Jacobian."""
+    BlockQR() factors every block by column-pivoted QR in one pass (nb <= 64), QR() is refused as for every sparse
+    Jacobian."""
 
     def __init__(self, nblocks, mb, nb, data=None):
         nblocks, mb, nb = int(nblocks), int(mb), int(nb)
@@ -200,6 +209,14 @@ def default_solver(solver, J):
     if isinstance(solver, QR) and (_is_sparse(J) or _is_blockdiag(J)):
         raise ArgumentError(_lib.EARG, "solver QR() is not available for sparse Jacobians. "
                                        "Choose between Cholesky() and LSMR()")
+    if isinstance(solver, BlockQR):
+        if not _is_blockdiag(J):
+            raise ArgumentError(_lib.EARG, "BlockQR() needs a BlockDiagonal Jacobian with blocks of at most 64 columns "
+                                           "(got a %s of shape %s). Use QR() on a dense Jacobian, LSMR() on a sparse one"
+                                           % (type(J).__name__, tuple(getattr(J, "shape", ()))))
+        if J.nb > 64:
+            raise ArgumentError(_lib.EARG, "BlockQR() needs blocks of at most 64 columns (got %d blocks of %d x %d). "
+                                           "Use LSMR()" % (J.nblocks, J.mb, J.nb))
     return solver
 
 
@@ -617,7 +634,7 @@ class AllocatedSolver:
     def __init__(self, J, solver, for_lm):
         h = C.c_void_p()
         check(lib().lsq_solver_create(J.ctx.h, J.h, solver.kind, 1 if for_lm else 0, C.byref(h)))
-        self.h, self.J = h, J
+        self.h, self.J, self.kind = h, J, solver.kind
         self._pc = None
         if getattr(solver, "P", None) is not None:
             self._pc = _general_precond_trampolines(solver, J.ctx, J)
@@ -656,8 +673,12 @@ class AllocatedSolver:
         check(lib().lsq_solver_qr_panel(self.h, C.byref(panel)))
         bpath, bblock = C.c_int(0), C.c_int(-1)
         check(lib().lsq_solver_blockdiag_path(self.h, C.byref(bpath), C.byref(bblock)))
-        return dict(blockdiag_path={0: None, 1: "batched-unpivoted", 2: "batched-pivoted"}[bpath.value],
-                    blockdiag_block=bblock.value,
+        block_ranks = None
+        if self.kind == _lib.BLOCK_QR:
+            block_ranks = np.zeros(self.J.blockdiag_info()[0], dtype=np.int32)
+            check(lib().lsq_solver_blockdiag_ranks(self.h, block_ranks.ctypes.data_as(_lib.c_ip)))
+        return dict(blockdiag_path={0: None, 1: "batched-unpivoted", 2: "batched-pivoted", 3: "batched-qr"}[bpath.value],
+                    blockdiag_block=bblock.value, block_ranks=block_ranks,
                     lsmr_iter=it.value, lsmr_istop=st.value, qr_rank=rk.value,
                     qr_panel={0: None, 1: "householder-steps", 2: "cholqr2"}[panel.value],
                     qr_path={0: None, 1: "one-stage", 2: "two-stage-pivoted", 3: "two-stage-certified"}[path.value],
@@ -948,9 +969,9 @@ def optimize_(nls, optimizer=None, x_tol=1e-8, f_tol=1e-8, g_tol=1e-8, iteration
             raise TypeError("an allocated problem carries its optimizer (types.jl:152-157)")
         ctx, optimizer, solver = allocated.ctx, allocated.optimizer, allocated.solver
     else:
-        ctx = ctx or default_context()
-        solver = default_solver(optimizer.solver if optimizer is not None else None, nls.J)
+        solver = default_solver(optimizer.solver if optimizer is not None else None, nls.J)   # (refusals need no device)
         optimizer = default_optimizer(optimizer, solver)
+        ctx = ctx or default_context()
     n, m = len(nls.x), len(nls.y)
     is_op = isinstance(nls.J, DeviceOperator)
     if allocated is not None:
@@ -1069,7 +1090,7 @@ class BatchedResult:
             k = min(r.iterations, self.trace["ssr"].shape[0])
             r.trace = {key: self.trace[key][:k, b].copy() for key in ("ssr", "gnorm", "delta", "rho", "accept")}
             r.trace["x"] = self.trace["x"][:k, b * self.nb:(b + 1) * self.nb].copy()
-            # solves per iteration: Cholesky() is one, and Dogleg reuses its steps after a refused one (dogleg.jl:81)
+            # solves per iteration: Cholesky() and BlockQR() are one, and Dogleg reuses its steps after a refused one (dogleg.jl:81)
             inner = np.ones(k, dtype=np.int32)
             if self.optimizer == "Dogleg" and k > 1:
                 inner[1:] = r.trace["accept"][:k - 1]
@@ -1092,7 +1113,9 @@ def _batched_arguments(J, optimizer, n, lower, upper):
         raise ArgumentError(_lib.EARG, "optimize_batched_: LSMR() is not available per block (an iterative solve per block "
                                        "is a different loop). Use Cholesky(), or optimize_ for one trust region over the "
                                        "stacked problem")
-    if J.nb > 64:
+    if isinstance(solver, BlockQR):
+        default_solver(solver, J)
+    elif J.nb > 64:
         raise ArgumentError(_lib.EARG, "optimize_batched_: Cholesky() per block needs blocks of at most 64 columns "
                                        "(got nb = %d)" % J.nb)
     for bound in (lower, upper):

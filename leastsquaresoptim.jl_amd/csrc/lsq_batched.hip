@@ -123,7 +123,7 @@ k_bt_init(int B, int mb, int nb, BtDev s, BtOpt o, const double *__restrict__ x,
 // Dogleg: dogleg.jl:85-160 (sol = the Gauss-Newton step of the blocks that were solved in this iteration).
 template <bool LM>
 __global__ void __launch_bounds__(256)
-k_bt_step(int B, int mb, int nb, BtDev s, const double *__restrict__ vals, const double *__restrict__ scale,
+k_bt_step(int B, int mb, int nb, BtDev s, bool qr, const double *__restrict__ vals, const double *__restrict__ scale,
           const int *__restrict__ binfo, const double *__restrict__ grad, const double *__restrict__ diag,
           double *__restrict__ dtd, double *__restrict__ dgr, const double *__restrict__ dgn, const double *__restrict__ x,
           const double *__restrict__ lo, const double *__restrict__ hi, double *__restrict__ dx, double *__restrict__ xt) {
@@ -139,7 +139,9 @@ k_bt_step(int B, int mb, int nb, BtDev s, const double *__restrict__ vals, const
     const int iter = s.iter[b] + 1;
     const bool fresh = LM ? true : s.reuse[b] == 0;      // the block was solved in this iteration
     const int needj = LM ? s.needj[b] : (fresh ? 1 : 0);
-    if (fresh && binfo[b] != 0) {
+    if (qr) {                  // BlockQR(): no block fails on rank; binfo[b] is the rank of the solve
+        if (fresh && lane == 0) s.info[b] = binfo[b];
+    } else if (fresh && binfo[b] != 0) {
         // dense_cholesky.jl:57 PosDefException / :33 RankDeficientException of THIS block: frozen with the iterate it holds;
         // the counts are those of the reference at the throw (iter, g!; Dogleg: the two products in front of the solve)
         if (in) { xt[j] = xv; dx[j] = 0.0; }
@@ -334,7 +336,7 @@ struct BtBuffers {
 };
 
 template <bool LM>
-int bt_loop(lsq_ctx *c, lsq_mat *J, double *x, double *fcur, lsq_f_callback f, lsq_g_callback g, void *user,
+int bt_loop(lsq_ctx *c, lsq_mat *J, bool qr, double *x, double *fcur, lsq_f_callback f, lsq_g_callback g, void *user,
             const lsq_options *o, lsq_batched_result *r) {
     const int B = J->bd_blocks, mb = J->bd_mb, nb = J->bd_nb, m = J->m, n = J->n;
     BtBuffers buf{c->stream};
@@ -392,9 +394,10 @@ int bt_loop(lsq_ctx *c, lsq_mat *J, double *x, double *fcur, lsq_f_callback f, l
         // differ from that point in the last bit (levenberg_marquardt.jl:135)
         if (cnt[1] > 0) LSQ_TRY(lsq_call_g(g, J, xg, user));
         LSQ_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(int), c->stream));
-        LSQ_TRY(lsq_blockdiag_solve_blocks(c, J, !LM, fcur, s.delta, LM ? dx : dgn, s.solve, binfo, grad, diag));
+        if (qr) LSQ_TRY(lsq_blockqr_solve_blocks(c, J, LM, fcur, s.delta, LM ? dx : dgn, s.solve, binfo, grad, diag));
+        else LSQ_TRY(lsq_blockdiag_solve_blocks(c, J, !LM, fcur, s.delta, LM ? dx : dgn, s.solve, binfo, grad, diag));
         const double *vals = J->csc.d_val, *scale = J->d_colscale;
-        LSQ_LAUNCH(k_bt_step<LM>, grid, blk, 0, c->stream, B, mb, nb, s, vals, scale, (const int *)binfo, (const double *)grad,
+        LSQ_LAUNCH(k_bt_step<LM>, grid, blk, 0, c->stream, B, mb, nb, s, qr, vals, scale, (const int *)binfo, (const double *)grad,
                    (const double *)diag, dtd, dgr, (const double *)dgn, (const double *)x, (const double *)lo, (const double *)hi,
                    dx, xt);
         LSQ_HIP(hipGetLastError());
@@ -468,8 +471,14 @@ extern "C" int lsq_optimize_batched(lsq_ctx *c, int optimizer, int solver_kind, 
                       "loop). Use Cholesky(), or lsq_optimize for one trust region over the stacked problem");
         return LSQ_EARG;
     }
-    if (solver_kind != LSQ_CHOLESKY) {
+    if (solver_kind != LSQ_CHOLESKY && solver_kind != LSQ_BLOCK_QR) {
         lsq_set_error("lsq_optimize_batched: unknown solver %d", solver_kind);
+        return LSQ_EARG;
+    }
+    const bool qr = solver_kind == LSQ_BLOCK_QR;
+    if (qr && J->bd_nb > 64) {
+        lsq_set_error("lsq_optimize_batched: BlockQR() needs blocks of at most 64 columns (got %d blocks of %d x %d): one "
+                      "block's triangular factor must fit the in-LDS factorisation", J->bd_blocks, J->bd_mb, J->bd_nb);
         return LSQ_EARG;
     }
     if (J->bd_nb > 64) {
@@ -498,8 +507,8 @@ extern "C" int lsq_optimize_batched(lsq_ctx *c, int optimizer, int solver_kind, 
             }
     }
     auto t0 = std::chrono::steady_clock::now();
-    const int st = optimizer == LSQ_LEVENBERG_MARQUARDT ? bt_loop<true>(c, J, x, fcur, f, g, user, opt, res)
-                                                        : bt_loop<false>(c, J, x, fcur, f, g, user, opt, res);
+    const int st = optimizer == LSQ_LEVENBERG_MARQUARDT ? bt_loop<true>(c, J, qr, x, fcur, f, g, user, opt, res)
+                                                        : bt_loop<false>(c, J, qr, x, fcur, f, g, user, opt, res);
     hipStreamSynchronize(c->stream);
     res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return st;

@@ -40,7 +40,8 @@ extern "C" int lsq_solver_create(lsq_ctx *c, lsq_mat *J, int kind, int for_lm, l
     s->for_lm = for_lm ? 1 : 0;
     s->m = J->m;
     s->n = J->n;
-    int st = (kind == LSQ_LSMR) ? lsq_lsmr_alloc(s) : blockdiag ? lsq_blockdiag_solver_alloc(s, J) : lsq_dense_solver_alloc(s);
+    int st = (kind == LSQ_LSMR) ? lsq_lsmr_alloc(s) : (kind == LSQ_BLOCK_QR) ? lsq_blockqr_solver_alloc(s, J)
+             : blockdiag ? lsq_blockdiag_solver_alloc(s, J) : lsq_dense_solver_alloc(s);
     if (st != LSQ_OK) {
         delete s;
         return st;
@@ -53,7 +54,7 @@ extern "C" int lsq_solver_destroy(lsq_solver *s) {
     if (!s) return LSQ_OK;
     hipStreamSynchronize(s->ctx->stream);
     if (s->kind == LSQ_LSMR) lsq_lsmr_free(s);
-    else lsq_dense_solver_free(s);
+    else lsq_dense_solver_free(s);     // (also the block-diagonal solvers: all they own is d_info, freed there)
     delete s;
     return LSQ_OK;
 }
@@ -85,6 +86,7 @@ extern "C" int lsq_ldiv(lsq_solver *s, lsq_mat *J, const double *y, double *x, i
     switch (s->kind) {
     case LSQ_LSMR: LSQ_TRY(lsq_lsmr_solve(s, J, y, nullptr, x, nmul)); return lsmr_drain(s);
     case LSQ_CHOLESKY: return s->bd_blocks ? lsq_blockdiag_solve(s, J, y, nullptr, x, nmul) : lsq_cholesky_solve(s, J, y, nullptr, x, nmul);
+    case LSQ_BLOCK_QR: return lsq_blockqr_solve(s, J, y, nullptr, x, nmul);
     default: return lsq_qr_solve(s, J, y, nullptr, x, nmul);
     }
 }
@@ -95,6 +97,7 @@ extern "C" int lsq_ldiv_damped(lsq_solver *s, lsq_mat *J, const double *y, doubl
     switch (s->kind) {
     case LSQ_LSMR: LSQ_TRY(lsq_lsmr_solve(s, J, y, damp, x, nmul)); return lsmr_drain(s);
     case LSQ_CHOLESKY: return s->bd_blocks ? lsq_blockdiag_solve(s, J, y, damp, x, nmul) : lsq_cholesky_solve(s, J, y, damp, x, nmul);
+    case LSQ_BLOCK_QR: return lsq_blockqr_solve(s, J, y, damp, x, nmul);
     default: return lsq_qr_solve(s, J, y, damp, x, nmul);
     }
 }
@@ -145,6 +148,11 @@ extern "C" int lsq_solver_info(const lsq_solver *s, int *iter, int *istop, int *
         if (s->kind == LSQ_QR && s->d_info) {
             LSQ_HIP(hipStreamSynchronize(s->ctx->stream));
             LSQ_HIP(hipMemcpy(rank, s->d_info, sizeof(int), hipMemcpyDeviceToHost));
+        } else if (s->kind == LSQ_BLOCK_QR && s->bq_solved) {    // the sum of the block ranks
+            std::vector<int> hr((size_t)s->bd_blocks);
+            LSQ_TRY(lsq_solver_blockdiag_ranks(s, hr.data()));
+            *rank = 0;
+            for (int v : hr) *rank += v;
         }
     }
     return LSQ_OK;

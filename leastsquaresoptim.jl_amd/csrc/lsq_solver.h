@@ -121,6 +121,8 @@ struct lsq_solver {
     int bd_blocks = 0, bd_mb = 0, bd_nb = 0;
     int last_bd_path = 0;           // lsq_solver_blockdiag_path
     int last_bd_block = -1;
+    // --- BlockQR() on the same handles (lsq_blockqr.hip): d_info holds the bd_blocks ranks of the last solve ---
+    bool bq_solved = false;
 };
 int lsq_tri_chol_solve(lsq_solver *s, const double *U, int n, double *d_bx);
 int lsq_tri_chol_fwd_operands(lsq_solver *s, int n, double **z, unsigned long long **slot, unsigned long long *epoch, int **err);
@@ -233,5 +235,10 @@ int lsq_blockdiag_solver_alloc(lsq_solver *s, const lsq_mat *J);
 int lsq_blockdiag_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);
 int lsq_blockdiag_solve_blocks(lsq_ctx *c, lsq_mat *J, bool pivot, const double *d_y, const double *d_delta, double *d_x,
                                const int *d_active, int *d_binfo, double *d_r, double *d_diag);
+// implemented in lsq_blockqr.hip
+int lsq_blockqr_solver_alloc(lsq_solver *s, const lsq_mat *J);
+int lsq_blockqr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);
+int lsq_blockqr_solve_blocks(lsq_ctx *c, lsq_mat *J, bool lm, const double *d_y, const double *d_delta, double *d_x,
+                             const int *d_active, int *d_ranks, double *d_r, double *d_diag);
 // implemented in lsq_optimize.hip: g!(J, x) with the handle's bookkeeping around it (version, mirrors)
 int lsq_call_g(lsq_g_callback g, lsq_mat *J, const double *x, void *user);

@@ -1,4 +1,4 @@
-"""Measurements of Cholesky() on block-diagonal Jacobians (lsq_blockdiag.hip); one JSON line per run.
+"""Measurements of Cholesky() and BlockQR() on block-diagonal Jacobians (lsq_blockdiag.hip, lsq_blockqr.hip); one JSON line per run.
 
     python tools/blockdiag_bench.py dense      block solve vs the dense handle's Cholesky() on the stacked matrix
                                                (B=32, mb=512, nb=64: 16384 x 2048, the C3 shape)
@@ -7,6 +7,10 @@
                                                B=65536, mb=64, nb=8
     python tools/blockdiag_bench.py lm         LM(Cholesky()) on the block handle vs LM(LSMR()) on a plain CSC handle of the
                                                same matrix (B=8192, mb=256, nb=32): seconds per outer iteration, to convergence
+    python tools/blockdiag_bench.py qr         one BlockQR() solve (lsq_blockqr.hip), damped and undamped, against Cholesky() on
+                                               the same handle and the HBM floor 8 B mb (nb+1) bytes: B=4096 with 256 x 16,
+                                               128 x 32 and 64 x 64 blocks; and against the dense handle's QR() on 16 blocks of
+                                               128 x 32 stacked to 2048 x 512
     python tools/blockdiag_bench.py all
     python tools/blockdiag_bench.py lm --batched   one trust region per block (lsq_optimize_batched) against the stacked loop on
                                                the heterogeneous tanh problem (block b starts from 0.3 (b mod 4) (+1, -1, ..),
@@ -115,6 +119,42 @@ def bench_roofline(ctx, reps):
         Jd.free()
 
 
+def bench_qr(ctx, reps):
+    for B, mb, nb in ((4096, 256, 16), (4096, 128, 32), (4096, 64, 64)):
+        J, y, damp = block_operands(ctx, B, mb, nb, 3)
+        Jd = lsq.DeviceMatrix(ctx, J)
+        dx, dy, dd = lsq.DeviceVector(ctx, Jd.n), lsq.DeviceVector(ctx, Jd.m, y), lsq.DeviceVector(ctx, Jd.n, damp)
+        floor_bytes = 8.0 * B * mb * (nb + 1)
+        out = {"bench": "blockqr_vs_cholesky", "B": B, "mb": mb, "nb": nb, "floor_bytes": floor_bytes,
+               "floor_s_at_6.3TBs": floor_bytes / (ACHIEVABLE_TBS * 1e12)}
+        xs = {}
+        for name, solver in (("blockqr", lsq.BlockQR()), ("cholesky", lsq.Cholesky())):
+            for leg, d in (("damped", dd), ("undamped", None)):
+                sv = lsq.AllocatedSolver(Jd, solver, for_lm=d is not None)
+                out[name + "_" + leg] = time_solve(ctx, sv, dx, dy, d, reps)
+                xs[name + "_" + leg] = dx.get()
+        for leg in ("damped", "undamped"):
+            out["rel_diff_" + leg] = float(np.linalg.norm(xs["blockqr_" + leg] - xs["cholesky_" + leg]) /
+                                           np.linalg.norm(xs["cholesky_" + leg]))
+            out["qr_over_cholesky_" + leg] = out["blockqr_" + leg]["event_median_s"] / out["cholesky_" + leg]["event_median_s"]
+            out["qr_over_floor_" + leg] = out["blockqr_" + leg]["event_median_s"] / out["floor_s_at_6.3TBs"]
+        print(json.dumps(out))
+        Jd.free()
+    B, mb, nb = 16, 128, 32
+    J, y, damp = block_operands(ctx, B, mb, nb, 3)
+    out = {"bench": "blockqr_vs_dense_qr", "B": B, "mb": mb, "nb": nb}
+    xs = {}
+    for name, host, solver in (("blockqr", J, lsq.BlockQR()), ("dense_qr", J.toarray(), lsq.QR())):
+        Jd = lsq.DeviceMatrix(ctx, host)
+        dx, dy = lsq.DeviceVector(ctx, Jd.n), lsq.DeviceVector(ctx, Jd.m, y)
+        sv = lsq.AllocatedSolver(Jd, solver, for_lm=False)
+        out[name] = time_solve(ctx, sv, dx, dy, None, reps)
+        xs[name] = dx.get()
+    out["rel_diff"] = float(np.linalg.norm(xs["blockqr"] - xs["dense_qr"]) / np.linalg.norm(xs["dense_qr"]))
+    out["speedup_event_median"] = out["dense_qr"]["event_median_s"] / out["blockqr"]["event_median_s"]
+    print(json.dumps(out))
+
+
 def bench_lm(ctx, reps):
     B, mb, nb = 8192, 256, 32
     m, n = B * mb, B * nb
@@ -184,7 +224,7 @@ def bench_batched(ctx, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["dense", "roofline", "lm", "all"])
+    ap.add_argument("what", choices=["dense", "roofline", "lm", "qr", "all"])
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--batched", action="store_true", help="the per-block trust-region loop against the stacked one (only this leg)")
     a = ap.parse_args()
@@ -198,6 +238,8 @@ def main():
         bench_roofline(ctx, max(a.reps, 10))
     if a.what in ("lm", "all"):
         bench_lm(ctx, max(a.reps, 10))
+    if a.what in ("qr", "all"):
+        bench_qr(ctx, max(a.reps, 10))
 
 
 if __name__ == "__main__":
