@@ -83,6 +83,25 @@ int lsq_csc_create(lsq_ctx *ctx, int m, int n, const int *h_colptr, const int *h
 int lsq_blockdiag_create(lsq_ctx *ctx, int nblocks, int mb, int nb, lsq_mat **out);
 /* 0 blocks for any other handle */
 int lsq_mat_blockdiag_info(const lsq_mat *J, int *nblocks, int *mb, int *nb);
+/* J = [blkdiag(J_1 .. J_B) | C], the Jacobian of a GLOBAL fit: every data set b has its own nb local parameters (J_b dense
+ * mb x nb) and ng parameters are shared by all of them (C dense, (B*mb) x ng): m = B*mb, n = B*nb + ng.  Columns 0 .. B*nb-1
+ * are the block columns exactly as in lsq_blockdiag_create, columns B*nb .. n-1 the border, each with all m rows.  Values are
+ * addressed like a CSC handle with that pattern: nzval order = B column-major mb x nb blocks back to back, then ng columns of
+ * m doubles.  The handle IS a CSC handle (products, column sums, LSMR(), column scaling, value upload / refresh, sharding:
+ * unchanged) that also knows its shape.  lsq_mat_blockdiag_info answers "0 blocks" for it: the shared columns couple the
+ * blocks, so LSQ_BLOCK_QR, lsq_optimize_batched and the per-block Cholesky() refuse it like any other CSC handle.
+ * lsq_solver_create accepts it with LSQ_CHOLESKY and for_lm = 1 when nb + ng <= 64 (else LSQ_EARG): J'J + diag(damp) is an
+ * arrowhead, with the locals ordered first its Cholesky factor has no fill, and eliminating the locals block by block, then
+ * factoring the ng x ng Schur complement IS right-looking dpotrf on the stacked matrix -- so lsq_ldiv_damped and lsq_optimize
+ * with LSQ_LEVENBERG_MARQUARDT keep the reference's semantics (dense_cholesky.jl:43-59: one trust region, LSQ_ENOTPD with the
+ * 1-based column at which the stacked factorisation stops) at the cost of one pass over the values.  nmul is 1, damp is
+ * left as it is, a column-scaled handle means J S.  for_lm = 0 and lsq_ldiv (Dogleg(Cholesky())) are refused with LSQ_EARG on
+ * purpose: the reference factors with diagonal pivoting over the whole stacked matrix (dense_cholesky.jl:29-35) and reports
+ * RankDeficientException(rank) along that global pivot order, which does not split into "locals first".  LSQ_QR stays
+ * refused.  Any of the four sizes < 1, or sizes past 32-bit indices: LSQ_EDIM. */
+int lsq_blockdiag_bordered_create(lsq_ctx *ctx, int nblocks, int mb, int nb, int ng, lsq_mat **out);
+/* all 0 for any other handle */
+int lsq_mat_bordered_info(const lsq_mat *J, int *nblocks, int *mb, int *nb, int *ng);
 int lsq_mat_destroy(lsq_mat *J);
 int lsq_mat_size(const lsq_mat *J, int *m, int *n, long long *nnz);
 /* Upload values after a host-side g!(J, x): dense m*n column-major, or nzval in CSC order. */
@@ -232,7 +251,8 @@ int lsq_solver_qr_panel(const lsq_solver *s, int *kind);
  * n <= 1408; repeated as 2 if one of its bounded waits gives up) */
 int lsq_solver_chol_path(const lsq_solver *s, int *path);
 /* diagnostics of the last block solve: which path (0 none yet, 1 batched unpivoted LM, 2 batched pivoted Dogleg, 3 batched
- * per-block pivoted QR: LSQ_BLOCK_QR, block = -1) and, after LSQ_ENOTPD / LSQ_ERANK, the block that decided it (else -1) */
+ * per-block pivoted QR: LSQ_BLOCK_QR, block = -1, 4 bordered Schur, LM: lsq_blockdiag_bordered_create) and, after LSQ_ENOTPD /
+ * LSQ_ERANK, the block that decided it (path 4: nblocks when the Schur factor of the shared columns failed) (else -1) */
 int lsq_solver_blockdiag_path(const lsq_solver *s, int *path, int *block);
 /* LSQ_BLOCK_QR: the numerical rank of every block in the last solve (h_ranks: nblocks ints; -1 before the first solve).
  * LSQ_EARG for a solver of another kind. */

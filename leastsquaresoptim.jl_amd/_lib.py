@@ -113,6 +113,8 @@ def lib():
         "lsq_csc_create": (i, [vp, i, i, c_ip, c_ip, pvp]),
         "lsq_blockdiag_create": (i, [vp, i, i, i, pvp]),
         "lsq_mat_blockdiag_info": (i, [vp, c_ip, c_ip, c_ip]),
+        "lsq_blockdiag_bordered_create": (i, [vp, i, i, i, i, pvp]),
+        "lsq_mat_bordered_info": (i, [vp, c_ip, c_ip, c_ip, c_ip]),
         "lsq_mat_destroy": (i, [vp]),
         "lsq_mat_size": (i, [vp, c_ip, c_ip, C.POINTER(C.c_longlong)]),
         "lsq_mat_set_values": (i, [vp, c_dp]),

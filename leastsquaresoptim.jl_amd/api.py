@@ -199,13 +199,120 @@ def _is_blockdiag(J):
     return isinstance(J, BlockDiagonal)
 
 
+class BorderedBlockDiagonal:
+    """J = [blkdiag(J_1 .. J_B) | C]: the Jacobian of a GLOBAL fit -- data set b has its own nb local parameters (J_b dense
+    mb x nb) and ng parameters are shared by all data sets (C dense (B*mb) x ng; C_b = its rows of block b).  m = B*mb
+    residuals, n = B*nb + ng parameters, the shared ones last.  The same kind of host-side container as BlockDiagonal:
+    `.data` is the flat value array g_ overwrites, ordered as the nzval of `.tocsc()` -- B column-major mb x nb blocks back
+    to back, then the ng border columns of m values each.
+    On the device it becomes a CSC handle that knows its shape (lsq_blockdiag_bordered_create): LSMR() is the default solver,
+    Cholesky() eliminates the locals block by block and factors the ng x ng Schur complement (nb + ng <= 64;
+    LevenbergMarquardt only), QR() and BlockQR() are refused."""
+
+    def __init__(self, nblocks, mb, nb, ng, data=None):
+        nblocks, mb, nb, ng = int(nblocks), int(mb), int(nb), int(ng)
+        if nblocks < 1 or mb < 1 or nb < 1 or ng < 1:
+            raise DimensionMismatch(_lib.EDIM, "BorderedBlockDiagonal needs nblocks >= 1, mb >= 1, nb >= 1, ng >= 1 "
+                                               "(got %d, %d, %d, %d)" % (nblocks, mb, nb, ng))
+        self.nblocks, self.mb, self.nb, self.ng = nblocks, mb, nb, ng
+        self.shape = (nblocks * mb, nblocks * nb + ng)
+        self.nnz = nblocks * mb * (nb + ng)
+        if data is None:
+            self.data = np.zeros(self.nnz)
+        else:
+            d = np.ascontiguousarray(data, dtype=np.float64).reshape(-1)
+            if d.size != self.nnz:
+                raise DimensionMismatch(_lib.EDIM, "BorderedBlockDiagonal: expected %d values, got %d" % (self.nnz, d.size))
+            self.data = d
+
+    @classmethod
+    def from_blocks(cls, blocks, border):
+        """From a sequence of equally shaped (mb, nb) arrays and the (B*mb, ng) border."""
+        blocks = [np.asarray(b, dtype=np.float64) for b in blocks]
+        if not blocks or blocks[0].ndim != 2:
+            raise DimensionMismatch(_lib.EDIM, "BorderedBlockDiagonal.from_blocks needs a non-empty sequence of matrices")
+        mb, nb = blocks[0].shape
+        for k, b in enumerate(blocks):
+            if b.shape != (mb, nb):
+                raise DimensionMismatch(_lib.EDIM, "BorderedBlockDiagonal.from_blocks: block %d is %s, block 0 is %s"
+                                        % (k, b.shape, (mb, nb)))
+        border = np.asarray(border, dtype=np.float64)
+        if border.ndim != 2 or border.shape[0] != len(blocks) * mb or border.shape[1] < 1:
+            raise DimensionMismatch(_lib.EDIM, "BorderedBlockDiagonal.from_blocks: the border is %s, expected (%d, ng >= 1)"
+                                    % (border.shape, len(blocks) * mb))
+        out = cls(len(blocks), mb, nb, border.shape[1])
+        for k, b in enumerate(blocks):
+            out.block(k)[:, :] = b
+        out.border[:, :] = border
+        return out
+
+    def block(self, b):
+        """Block b as an (mb, nb) VIEW into `.data` (as it is bound at the time of the call)."""
+        if not 0 <= b < self.nblocks:
+            raise IndexError("block %d of %d" % (b, self.nblocks))
+        sz = self.mb * self.nb
+        return self.data[b * sz:(b + 1) * sz].reshape((self.mb, self.nb), order="F")
+
+    @property
+    def border(self):
+        """The shared columns as an (m, ng) column-major VIEW into `.data`."""
+        return self.data[self.nblocks * self.mb * self.nb:].reshape((self.shape[0], self.ng), order="F")
+
+    def border_block(self, b):
+        """C_b: rows b*mb .. of the border, an (mb, ng) VIEW into `.data`."""
+        if not 0 <= b < self.nblocks:
+            raise IndexError("block %d of %d" % (b, self.nblocks))
+        return self.border[b * self.mb:(b + 1) * self.mb, :]
+
+    def tocsc(self):
+        """The same matrix as scipy.sparse.csc_matrix (canonical order: `.data` of the result equals `.data` here)."""
+        if _sp is None:     # pragma: no cover
+            raise RuntimeError("BorderedBlockDiagonal.tocsc needs scipy")
+        m, n = self.shape
+        nloc = self.nblocks * self.nb
+        indptr = np.concatenate([np.arange(nloc + 1, dtype=np.int64) * self.mb,
+                                 nloc * self.mb + np.arange(1, self.ng + 1, dtype=np.int64) * m])
+        rows = (np.arange(self.nblocks, dtype=np.int64)[:, None, None] * self.mb +
+                np.zeros((1, self.nb, 1), dtype=np.int64) + np.arange(self.mb, dtype=np.int64)[None, None, :]).reshape(-1)
+        rows = np.concatenate([rows, np.tile(np.arange(m, dtype=np.int64), self.ng)])
+        return _sp.csc_matrix((self.data.copy(), rows.astype(np.int32), indptr.astype(np.int32)), shape=(m, n))
+
+    def toarray(self):
+        out = np.zeros(self.shape)
+        for b in range(self.nblocks):
+            out[b * self.mb:(b + 1) * self.mb, b * self.nb:(b + 1) * self.nb] = self.block(b)
+        out[:, self.nblocks * self.nb:] = self.border
+        return out
+
+
+BORDERED_DOGLEG_TEXT = ("Dogleg(Cholesky()) is not available on a bordered block-diagonal Jacobian: the reference's pivoted "
+                        "factorisation orders local and shared columns together, which does not split into blocks. "
+                        "Use LevenbergMarquardt(Cholesky()) or LSMR()")
+
+
+def _is_bordered(J):
+    return isinstance(J, BorderedBlockDiagonal)
+
+
+
 def default_solver(solver, J):
     """types.jl:114-121"""
     matrix_free = type(J).__name__ == "DeviceOperator"
     if solver is None:
-        return LSMR() if (_is_sparse(J) or _is_blockdiag(J) or matrix_free) else QR()
+        return LSMR() if (_is_sparse(J) or _is_blockdiag(J) or _is_bordered(J) or matrix_free) else QR()
     if matrix_free and not isinstance(solver, LSMR):
         raise ArgumentError(_lib.EARG, "a matrix-free Jacobian works with LSMR() only (README.md:37-47)")
+    if _is_bordered(J):
+        if isinstance(solver, QR):
+            raise ArgumentError(_lib.EARG, "solver QR() is not available for a BorderedBlockDiagonal Jacobian. "
+                                           "Choose between Cholesky() and LSMR()")
+        if isinstance(solver, BlockQR):
+            raise ArgumentError(_lib.EARG, "BlockQR() is not available for a BorderedBlockDiagonal Jacobian: the shared columns "
+                                           "couple the blocks. Choose between Cholesky() and LSMR()")
+        if isinstance(solver, Cholesky) and J.nb + J.ng > 64:
+            raise ArgumentError(_lib.EARG, "Cholesky() on a BorderedBlockDiagonal Jacobian needs nb + ng <= 64 "
+                                           "(got nb = %d, ng = %d). Use LSMR()" % (J.nb, J.ng))
+        return solver
     if isinstance(solver, QR) and (_is_sparse(J) or _is_blockdiag(J)):
         raise ArgumentError(_lib.EARG, "solver QR() is not available for sparse Jacobians. "
                                        "Choose between Cholesky() and LSMR()")
@@ -220,8 +327,13 @@ def default_solver(solver, J):
     return solver
 
 
-def default_optimizer(optimizer, solver):
-    """types.jl:123-127"""
+def default_optimizer(optimizer, solver, J=None):
+    """types.jl:123-127.  On a BorderedBlockDiagonal J, Cholesky() comes with LevenbergMarquardt (Dogleg(Cholesky()) does not
+    exist there and is refused)."""
+    if _is_bordered(J) and isinstance(solver, Cholesky):
+        if isinstance(optimizer, Dogleg):
+            raise ArgumentError(_lib.EARG, BORDERED_DOGLEG_TEXT)
+        return LevenbergMarquardt(solver)
     if isinstance(optimizer, Dogleg):
         return Dogleg(solver)
     if isinstance(optimizer, LevenbergMarquardt):
@@ -371,7 +483,16 @@ class DeviceMatrix:
         h = C.c_void_p()
         L = lib()
         self.blockdiag = None
-        if _is_blockdiag(J):
+        self.bordered = None
+        if _is_bordered(J):
+            self.sparse = True          # (values are addressed like a CSC handle's nzval)
+            self.bordered = (J.nblocks, J.mb, J.nb, J.ng)
+            self.m, self.n = J.shape
+            check(L.lsq_blockdiag_bordered_create(ctx.h, J.nblocks, J.mb, J.nb, J.ng, C.byref(h)))
+            self.h = h
+            self.nnz = J.nnz
+            self.set_values(J.data)
+        elif _is_blockdiag(J):
             self.sparse = True          # (values are addressed like a CSC handle's nzval)
             self.blockdiag = (J.nblocks, J.mb, J.nb)
             self.m, self.n = J.shape
@@ -428,6 +549,12 @@ class DeviceMatrix:
         a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
         check(lib().lsq_mat_blockdiag_info(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
+
+    def bordered_info(self):
+        """lsq_mat_bordered_info: (nblocks, mb, nb, ng); (0, 0, 0, 0) for a handle that is not bordered block-diagonal."""
+        a, b, c, d = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        check(lib().lsq_mat_bordered_info(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return a.value, b.value, c.value, d.value
 
     def set_colscale(self, s):
         """J = V diag(s) (lsq_mat_set_colscale): the values held now are V, `s` a DeviceVector of n factors that stays alive
@@ -677,7 +804,8 @@ class AllocatedSolver:
         if self.kind == _lib.BLOCK_QR:
             block_ranks = np.zeros(self.J.blockdiag_info()[0], dtype=np.int32)
             check(lib().lsq_solver_blockdiag_ranks(self.h, block_ranks.ctypes.data_as(_lib.c_ip)))
-        return dict(blockdiag_path={0: None, 1: "batched-unpivoted", 2: "batched-pivoted", 3: "batched-qr"}[bpath.value],
+        return dict(blockdiag_path={0: None, 1: "batched-unpivoted", 2: "batched-pivoted", 3: "batched-qr",
+                                    4: "bordered-schur"}[bpath.value],
                     blockdiag_block=bblock.value, block_ranks=block_ranks,
                     lsmr_iter=it.value, lsmr_istop=st.value, qr_rank=rk.value,
                     qr_panel={0: None, 1: "householder-steps", 2: "cholqr2"}[panel.value],
@@ -736,8 +864,8 @@ class LeastSquaresProblem:
         if type(J).__name__ == "DeviceOperator":
             if g_ is None:
                 raise ValueError("a matrix-free Jacobian needs g_ (it updates the operator's own state)")
-        elif _is_blockdiag(J):
-            pass              # g_ writes J.data ([block][column][row]) or the views J.block(b)
+        elif _is_blockdiag(J) or _is_bordered(J):
+            pass              # g_ writes J.data ([block][column][row], then the border) or the views J.block(b) / J.border
         elif _is_sparse(J):
             J = J.tocsc()
             J.sort_indices()  # g_ writes J.data in this (canonical CSC) order
@@ -765,7 +893,7 @@ def _central_difference_jacobian(f_, m):
     eps3 = np.finfo(float).eps ** (1.0 / 3.0)
 
     def g_(J, x):
-        if _is_sparse(J) or _is_blockdiag(J):
+        if _is_sparse(J) or _is_blockdiag(J) or _is_bordered(J):
             raise ArgumentError(_lib.EARG, "autodiff Jacobians are dense only (types.jl:57)")
         fp, fm = np.zeros(m), np.zeros(m)
         xp = np.array(x, dtype=np.float64)
@@ -960,7 +1088,10 @@ def optimize_(nls, optimizer=None, x_tol=1e-8, f_tol=1e-8, g_tol=1e-8, iteration
               store_trace=False, show_trace=False, show_every=1, lower=(), upper=(), ctx=None,
               full_trace=False, row_allreduce=None, global_rows=0):
     """optimize!(nls, optimizer; kwargs...)  -- types.jl:207-209 then
-    levenberg_marquardt.jl:39-144 / dogleg.jl:41-203.  Mutates nls.x, nls.y, nls.J in place."""
+    levenberg_marquardt.jl:39-144 / dogleg.jl:41-203.  Mutates nls.x, nls.y, nls.J in place.
+    On a BorderedBlockDiagonal Jacobian Cholesky() without an optimizer means LevenbergMarquardt(Cholesky()), and
+    Dogleg(Cholesky()) raises ArgumentError (it does not exist there); LevenbergMarquardt / Dogleg with LSMR() run as on any
+    sparse Jacobian."""
     allocated = nls if isinstance(nls, LeastSquaresProblemAllocated) else None
     if allocated is not None:
         # optimize!(nls::LeastSquaresProblemAllocated; kwargs...): buffers, solver and optimizer were chosen at
@@ -970,7 +1101,7 @@ def optimize_(nls, optimizer=None, x_tol=1e-8, f_tol=1e-8, g_tol=1e-8, iteration
         ctx, optimizer, solver = allocated.ctx, allocated.optimizer, allocated.solver
     else:
         solver = default_solver(optimizer.solver if optimizer is not None else None, nls.J)   # (refusals need no device)
-        optimizer = default_optimizer(optimizer, solver)
+        optimizer = default_optimizer(optimizer, solver, nls.J)
         ctx = ctx or default_context()
     n, m = len(nls.x), len(nls.y)
     is_op = isinstance(nls.J, DeviceOperator)
@@ -1100,6 +1231,9 @@ class BatchedResult:
 
 def _batched_arguments(J, optimizer, n, lower, upper):
     """Everything optimize_batched_ can refuse before a device call; returns (optimizer, solver)."""
+    if _is_bordered(J):
+        raise ArgumentError(_lib.EARG, "optimize_batched_ does not take a BorderedBlockDiagonal Jacobian: the shared columns "
+                                       "couple the blocks, so there is no trust region per block. Use optimize_")
     if not _is_blockdiag(J):
         raise ArgumentError(_lib.EARG, "optimize_batched_ needs a BlockDiagonal Jacobian: one trust region per block "
                                        "needs the block shape")
@@ -1212,7 +1346,7 @@ class LeastSquaresProblemAllocated:
             raise TypeError("LeastSquaresProblemAllocated(nls::LeastSquaresProblem, optimizer)")
         self.ctx = ctx or default_context()
         self.solver = default_solver(optimizer.solver if optimizer is not None else None, nls.J)
-        self.optimizer = default_optimizer(optimizer, self.solver)
+        self.optimizer = default_optimizer(optimizer, self.solver, nls.J)
         self.x, self.y, self.f_, self.J, self.g_ = nls.x, nls.y, nls.f_, nls.J, nls.g_
         self._Jd = nls.J if isinstance(nls.J, DeviceOperator) else DeviceMatrix(self.ctx, nls.J)
         self._dx = DeviceVector(self.ctx, len(nls.x), nls.x)

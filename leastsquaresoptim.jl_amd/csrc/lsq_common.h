@@ -282,6 +282,10 @@ struct lsq_mat {
     // block-diagonal Jacobian (lsq_blockdiag_create): a CSC handle that also knows its block shape -- J = blkdiag of
     // bd_blocks dense bd_mb x bd_nb blocks, nzval = the blocks column-major, back to back.  0 blocks: any other handle
     int bd_blocks = 0, bd_mb = 0, bd_nb = 0;
+    // bordered block-diagonal Jacobian (lsq_blockdiag_bordered_create): J = [blkdiag of br_blocks dense br_mb x br_nb blocks | br_ng
+    // dense columns of all m rows], nzval = the blocks as above, then the border column-major.  bd_* stay 0 on such a handle:
+    // the shared columns couple the blocks, so nothing that works block by block may take it.  0 blocks: any other handle
+    int br_blocks = 0, br_mb = 0, br_nb = 0, br_ng = 0;
 };
 
 // hipMemset runs on the NULL stream and is asynchronous to the host, while the library's stream is

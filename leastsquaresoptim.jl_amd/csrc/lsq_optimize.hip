@@ -28,7 +28,8 @@ extern "C" int lsq_solver_create(lsq_ctx *c, lsq_mat *J, int kind, int for_lm, l
         return LSQ_EARG;  // types.jl:115-117
     }
     const bool blockdiag = kind == LSQ_CHOLESKY && J->kind == LSQ_MAT_CSC && J->bd_blocks > 0;   // lsq_blockdiag_create
-    if (kind == LSQ_CHOLESKY && J->kind != LSQ_MAT_DENSE && !blockdiag) {
+    const bool bordered = kind == LSQ_CHOLESKY && J->kind == LSQ_MAT_CSC && J->br_blocks > 0;   // lsq_blockdiag_bordered_create
+    if (kind == LSQ_CHOLESKY && J->kind != LSQ_MAT_DENSE && !blockdiag && !bordered) {
         lsq_set_error("MethodError: no AbstractAllocatedSolver for Cholesky() with a sparse Jacobian "
                       "(dense_cholesky.jl:19 requires a StridedVecOrMat)");
         return LSQ_EARG;
@@ -41,7 +42,7 @@ extern "C" int lsq_solver_create(lsq_ctx *c, lsq_mat *J, int kind, int for_lm, l
     s->m = J->m;
     s->n = J->n;
     int st = (kind == LSQ_LSMR) ? lsq_lsmr_alloc(s) : (kind == LSQ_BLOCK_QR) ? lsq_blockqr_solver_alloc(s, J)
-             : blockdiag ? lsq_blockdiag_solver_alloc(s, J) : lsq_dense_solver_alloc(s);
+             : blockdiag ? lsq_blockdiag_solver_alloc(s, J) : bordered ? lsq_bordered_solver_alloc(s, J) : lsq_dense_solver_alloc(s);
     if (st != LSQ_OK) {
         delete s;
         return st;
@@ -85,7 +86,9 @@ extern "C" int lsq_ldiv(lsq_solver *s, lsq_mat *J, const double *y, double *x, i
     }
     switch (s->kind) {
     case LSQ_LSMR: LSQ_TRY(lsq_lsmr_solve(s, J, y, nullptr, x, nmul)); return lsmr_drain(s);
-    case LSQ_CHOLESKY: return s->bd_blocks ? lsq_blockdiag_solve(s, J, y, nullptr, x, nmul) : lsq_cholesky_solve(s, J, y, nullptr, x, nmul);
+    case LSQ_CHOLESKY:
+        if (s->br_blocks) return lsq_bordered_solve(s, J, y, nullptr, x, nmul);     // (refused: LM only)
+        return s->bd_blocks ? lsq_blockdiag_solve(s, J, y, nullptr, x, nmul) : lsq_cholesky_solve(s, J, y, nullptr, x, nmul);
     case LSQ_BLOCK_QR: return lsq_blockqr_solve(s, J, y, nullptr, x, nmul);
     default: return lsq_qr_solve(s, J, y, nullptr, x, nmul);
     }
@@ -96,7 +99,9 @@ extern "C" int lsq_ldiv_damped(lsq_solver *s, lsq_mat *J, const double *y, doubl
     if (!s || !J || !y || !x || !damp) return LSQ_EARG;
     switch (s->kind) {
     case LSQ_LSMR: LSQ_TRY(lsq_lsmr_solve(s, J, y, damp, x, nmul)); return lsmr_drain(s);
-    case LSQ_CHOLESKY: return s->bd_blocks ? lsq_blockdiag_solve(s, J, y, damp, x, nmul) : lsq_cholesky_solve(s, J, y, damp, x, nmul);
+    case LSQ_CHOLESKY:
+        if (s->br_blocks) return lsq_bordered_solve(s, J, y, damp, x, nmul);
+        return s->bd_blocks ? lsq_blockdiag_solve(s, J, y, damp, x, nmul) : lsq_cholesky_solve(s, J, y, damp, x, nmul);
     case LSQ_BLOCK_QR: return lsq_blockqr_solve(s, J, y, damp, x, nmul);
     default: return lsq_qr_solve(s, J, y, damp, x, nmul);
     }

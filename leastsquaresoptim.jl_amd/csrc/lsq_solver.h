@@ -123,6 +123,9 @@ struct lsq_solver {
     int last_bd_block = -1;
     // --- BlockQR() on the same handles (lsq_blockqr.hip): d_info holds the bd_blocks ranks of the last solve ---
     bool bq_solved = false;
+    // --- Cholesky() on a bordered block-diagonal Jacobian (lsq_bordered.hip): br_blocks > 0; d_info and d_work (the factor rows,
+    // the Schur contributions and their partial sums) are allocated ---
+    int br_blocks = 0, br_mb = 0, br_nb = 0, br_ng = 0;
 };
 int lsq_tri_chol_solve(lsq_solver *s, const double *U, int n, double *d_bx);
 int lsq_tri_chol_fwd_operands(lsq_solver *s, int n, double **z, unsigned long long **slot, unsigned long long *epoch, int **err);
@@ -235,6 +238,9 @@ int lsq_blockdiag_solver_alloc(lsq_solver *s, const lsq_mat *J);
 int lsq_blockdiag_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);
 int lsq_blockdiag_solve_blocks(lsq_ctx *c, lsq_mat *J, bool pivot, const double *d_y, const double *d_delta, double *d_x,
                                const int *d_active, int *d_binfo, double *d_r, double *d_diag);
+// implemented in lsq_bordered.hip
+int lsq_bordered_solver_alloc(lsq_solver *s, const lsq_mat *J);
+int lsq_bordered_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);
 // implemented in lsq_blockqr.hip
 int lsq_blockqr_solver_alloc(lsq_solver *s, const lsq_mat *J);
 int lsq_blockqr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);

@@ -38,6 +38,13 @@ def blockdiag_inputs(nblocks, mb, nb, seed):
     return dense_inputs(mb, nblocks * nb, seed)
 
 
+def bordered_inputs(nblocks, mb, nb, ng, seed):
+    """Values of [blkdiag(A_1 .. A_B) | C] in the order of a BorderedBlockDiagonal's `.data`: the blocks as blockdiag_inputs
+    draws them, then the border -- the dense generator's m x ng matrix (m = B*mb) at seed + 1, column-major, every entry
+    N(0,1)/sqrt(m)."""
+    return np.concatenate([blockdiag_inputs(nblocks, mb, nb, seed), dense_inputs(nblocks * mb, ng, seed + 1)])
+
+
 def uniform(n, seed, lo=-1.0, hi=1.0):
     v = np.zeros(n)
     check(lib().lsq_synth_uniform(n, seed, lo, hi, v.ctypes.data_as(_lib.c_dp)))
@@ -74,15 +81,33 @@ class _Handle:      # minimal handle wrapper for _run_native
 class TanhProblem:
     """Device-resident problem: Jacobian handle + model (A, b) + x / fcur vectors."""
 
-    def __init__(self, m, n, sparse=True, per_col=None, seed=BASE_SEED, ctx=None, inputs=None, b=None, blockdiag=None):
+    def __init__(self, m, n, sparse=True, per_col=None, seed=BASE_SEED, ctx=None, inputs=None, b=None, blockdiag=None,
+                 bordered=None):
         """blockdiag=(nblocks, mb, nb): A = blkdiag of nblocks dense mb x nb blocks (m = nblocks*mb, n = nblocks*nb) on a
-        block-diagonal handle (lsq_blockdiag_create); `inputs` / self.A are then the values in [block][column][row] order."""
+        block-diagonal handle (lsq_blockdiag_create); `inputs` / self.A are then the values in [block][column][row] order.
+        bordered=(nblocks, mb, nb, ng): A = [blkdiag | C] with ng shared columns (m = nblocks*mb, n = nblocks*nb + ng) on a
+        bordered handle (lsq_blockdiag_bordered_create); `inputs` / self.A are the values in bordered_inputs' order."""
         self.ctx = ctx or default_context()
         self.m, self.n, self.sparse = m, n, sparse
         self.blockdiag = None
+        self.bordered = None
         L = lib()
         h = C.c_void_p()
-        if blockdiag is not None:
+        if bordered is not None:
+            B, mb, nb, ng = (int(v) for v in bordered)
+            if (m, n) != (B * mb, B * nb + ng):
+                raise ValueError("bordered=(%d, %d, %d, %d) is a %d x %d problem, not %d x %d"
+                                 % (B, mb, nb, ng, B * mb, B * nb + ng, m, n))
+            self.bordered, self.sparse = (B, mb, nb, ng), True
+            if inputs is None:
+                inputs = bordered_inputs(B, mb, nb, ng, seed)
+            self.A = inputs
+            check(L.lsq_blockdiag_bordered_create(self.ctx.h, B, mb, nb, ng, C.byref(h)))
+            self.nnz = len(self.A)
+            A3 = self.A[:B * mb * nb].reshape((B, nb, mb))
+            Cg = self.A[B * mb * nb:].reshape((m, ng), order="F")
+            mv = lambda t: np.einsum("bjr,bj->br", A3, t[:B * nb].reshape((B, nb))).reshape(-1) + Cg @ t[B * nb:]
+        elif blockdiag is not None:
             B, mb, nb = (int(v) for v in blockdiag)
             if (m, n) != (B * mb, B * nb):
                 raise ValueError("blockdiag=(%d, %d, %d) is a %d x %d problem, not %d x %d" % (B, mb, nb, B * mb, B * nb, m, n))

@@ -11,7 +11,12 @@
                                                the same handle and the HBM floor 8 B mb (nb+1) bytes: B=4096 with 256 x 16,
                                                128 x 32 and 64 x 64 blocks; and against the dense handle's QR() on 16 blocks of
                                                128 x 32 stacked to 2048 x 512
-    python tools/blockdiag_bench.py all
+    python tools/blockdiag_bench.py bordered   Cholesky() on a BORDERED block-diagonal handle (lsq_bordered.hip): B=4096, mb=256 with
+                                               (nb, ng) = (8, 8) and (32, 16) -- one lsq_ldiv_damped against the HBM floor
+                                               8 B mb (nb+ng+1) bytes at 6.3 TB/s, and LM to convergence on the device tanh model
+                                               against LevenbergMarquardt(LSMR()) on the same handle (the only way to solve the
+                                               problem on the device without this solver)
+    python tools/blockdiag_bench.py all        (dense, roofline, lm, qr)
     python tools/blockdiag_bench.py lm --batched   one trust region per block (lsq_optimize_batched) against the stacked loop on
                                                the heterogeneous tanh problem (block b starts from 0.3 (b mod 4) (+1, -1, ..),
                                                0.1 N(0,1) added to the right-hand side of blocks b mod 8 == 5), device model,
@@ -182,6 +187,41 @@ def bench_lm(ctx, reps):
     pl.close()
 
 
+def bench_bordered(ctx, reps):
+    LM = lsq._lib.LEVENBERG_MARQUARDT
+    for nb, ng in ((8, 8), (32, 16)):
+        B, mb = 4096, 256
+        m, n = B * mb, B * nb + ng
+        pr = lsq.synthetic.TanhProblem(m, n, seed=4, ctx=ctx, bordered=(B, mb, nb, ng))
+        floor_bytes = 8.0 * B * mb * (nb + ng + 1)
+        out = {"bench": "bordered_cholesky", "B": B, "mb": mb, "nb": nb, "ng": ng, "floor_bytes": floor_bytes,
+               "floor_s_at_6.3TBs": floor_bytes / (ACHIEVABLE_TBS * 1e12)}
+        Jd = lsq.DeviceMatrix(ctx, lsq.BorderedBlockDiagonal(B, mb, nb, ng, data=pr.A))
+        rng = np.random.default_rng(5)
+        sv = lsq.AllocatedSolver(Jd, lsq.Cholesky(), for_lm=True)
+        dx, dy = lsq.DeviceVector(ctx, n), lsq.DeviceVector(ctx, m, rng.standard_normal(m))
+        dd = lsq.DeviceVector(ctx, n, 0.05 + rng.random(n))
+        out["ldiv_damped"] = time_solve(ctx, sv, dx, dy, dd, reps)
+        out["ldiv_damped_over_floor"] = out["ldiv_damped"]["event_median_s"] / out["floor_s_at_6.3TBs"]
+        sv.free()
+        Jd.free()
+        for name, kind in (("lm_cholesky", lsq._lib.CHOLESKY), ("lm_lsmr", lsq._lib.LSMR)):
+            runs = []
+            for k in range(2 + reps):
+                pr.reset()
+                r = pr.optimize(LM, kind, iterations=50, fetch_x=False)
+                if k >= 2:
+                    runs.append(r)
+            sec = [r.seconds for r in runs]
+            r = runs[-1]
+            out[name] = {"converged": r.converged, "outer_iterations": r.iterations, "lsmr_inner_iterations": r.lsmr_iterations,
+                         "ssr": r.ssr, "seconds_median": statistics.median(sec), "seconds_min": min(sec),
+                         "seconds_per_outer_median": statistics.median(sec) / max(r.iterations, 1), "reps": reps}
+        out["speedup_to_convergence"] = out["lm_lsmr"]["seconds_median"] / out["lm_cholesky"]["seconds_median"]
+        print(json.dumps(out), flush=True)
+        pr.close()
+
+
 def bench_batched(ctx, reps):
     LM, CH = lsq._lib.LEVENBERG_MARQUARDT, lsq._lib.CHOLESKY
     for B, mb, nb in ((4096, 256, 16), (4096, 128, 32)):
@@ -224,13 +264,16 @@ def bench_batched(ctx, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["dense", "roofline", "lm", "qr", "all"])
+    ap.add_argument("what", choices=["dense", "roofline", "lm", "qr", "bordered", "all"])
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--batched", action="store_true", help="the per-block trust-region loop against the stacked one (only this leg)")
     a = ap.parse_args()
     ctx = lsq.default_context()
     if a.batched:
         bench_batched(ctx, max(a.reps, 10))
+        return
+    if a.what == "bordered":
+        bench_bordered(ctx, max(a.reps, 10))
         return
     if a.what in ("dense", "all"):
         bench_dense(ctx, max(a.reps, 10))
