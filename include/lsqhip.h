@@ -257,6 +257,30 @@ int lsq_solver_blockdiag_path(const lsq_solver *s, int *path, int *block);
 /* LSQ_BLOCK_QR: the numerical rank of every block in the last solve (h_ranks: nblocks ints; -1 before the first solve).
  * LSQ_EARG for a solver of another kind. */
 int lsq_solver_blockdiag_ranks(const lsq_solver *s, int *h_ranks);
+/* Parameter covariance at the point where J was evaluated, for the many-small-fits handles: how well each parameter is
+ * determined, at the cost of ONE solve (one pass over the values) and without moving J to the host.  `s` is an LSQ_CHOLESKY
+ * solver created on J (it owns the scratch and the info words, as for the solves): on a block-diagonal handle
+ * (lsq_blockdiag_create, nb <= 64) either for_lm, on a bordered handle (lsq_blockdiag_bordered_create, nb + ng <= 64) for_lm = 1.
+ * Any other solver kind or handle, a handle whose shape differs from the one the solver was allocated for, or d_cov and
+ * d_stderr both NULL: LSQ_EARG with a message in lsq_last_error.  A column-scaled handle means J S, as everywhere else; no
+ * damping is involved.  d_f: NULL (the unscaled inv(J'J)) or the residual at that point (m doubles, device).  d_cov: NULL
+ * (only d_stderr is wanted) or the output below; d_stderr: NULL or n doubles, the square roots of the diagonal of what is
+ * (or would be) written to d_cov, in the order of the parameters.
+ *   Block-diagonal handle: d_cov is B*nb*nb doubles; block b at offset b*nb*nb is nb x nb, both triangles written with the
+ *   same bits, and holds s_b^2 inv(J_b'J_b) with s_b^2 = sum(f_b.^2) / (mb - nb) over the block's own mb rows -- the residual
+ *   variance of the B independent fits of lsq_optimize_batched -- or 1 without d_f.  mb <= nb with d_f: LSQ_EARG.  h_info: NULL
+ *   or B host ints, entry b = 0 or the 1-based column of block b at which the unpivoted dpotrf of J_b'J_b meets a pivot that is
+ *   not positive; such a block gets NaN in all of its cov and stderr entries, the other blocks are unaffected and the call
+ *   returns LSQ_OK.  (LSQ_BLOCK_QR is the tool for rank-deficient blocks; a pseudo-inverse covariance is not offered.)
+ *   Block b's result does not depend on the other blocks, on B, or on the run: same bits.
+ *   Bordered handle: d_cov is B*nb*nb + ng*ng doubles: the B diagonal blocks of s^2 inv(J'J) that belong to the locals, then
+ *   the ng x ng block of the shared parameters; ONE variance s^2 = sum(f.^2) / (m - n) (it is one fit), or 1 without d_f.
+ *   m <= n with d_f: LSQ_EARG.  If a local block or the Schur factor is not positive definite: LSQ_ENOTPD with the stacked
+ *   column exactly as lsq_ldiv_damped reports it (also in h_info[0] when h_info is given, else h_info[0] = 0), the block in
+ *   lsq_solver_blockdiag_path, and d_cov / d_stderr unspecified.  The local-shared cross-covariances -W_b Cov_gg
+ *   (W_b = inv(J_b'J_b) J_b'C_b) are NOT formed.
+ * Synchronises the stream when it has host results to return (h_info, the bordered handle's status); otherwise stream-ordered. */
+int lsq_solver_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double *d_cov, double *d_stderr, int *h_info);
 
 /* The fast paths above that rely on co-resident workgroups (one-launch Cholesky, pipelined triangular solves, the QR panel's slab
  * exchange + pipelined certified solve) wait with a bound; a wait that gives up makes the solve repeat itself on the

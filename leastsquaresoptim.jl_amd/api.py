@@ -812,6 +812,23 @@ class AllocatedSolver:
                     qr_path={0: None, 1: "one-stage", 2: "two-stage-pivoted", 3: "two-stage-certified"}[path.value],
                     chol_path={0: None, 1: "one-workgroup", 2: "blocked", 3: "blocked-certified", 4: "blocked-one-launch"}[cpath.value])
 
+    def covariance(self, f=None, stderr=True):
+        """lsq_solver_covariance at the values J holds now: a Covariance.  `f`: None (the unscaled inv(J'J)), or the residual
+        there (DeviceVector or m host values) -- per-block variances on a block-diagonal handle, one on a bordered handle."""
+        J = self.J
+        if J.bordered is not None:
+            B, _, nb, ng = J.bordered
+        elif J.blockdiag is not None:
+            (B, _, nb), ng = J.blockdiag, 0
+        else:
+            B, nb, ng = 0, 0, 0            # (refused by the library, with its message)
+        df = f if (f is None or hasattr(f, "ptr")) else DeviceVector(J.ctx, J.m, f)
+        dcov = DeviceVector(J.ctx, B * nb * nb + ng * ng)
+        dse = DeviceVector(J.ctx, J.n) if stderr else None
+        info = np.zeros(max(B, 1), dtype=np.int32)
+        check(lib().lsq_solver_covariance(self.h, J.h, _ptr(df), dcov.ptr, _ptr(dse), info.ctypes.data_as(_lib.c_ip)))
+        return Covariance(B, nb, ng, dcov.get(), dse.get() if stderr else None, info[:B] if not ng else None)
+
     def stats(self):
         """lsq_solver_stats: give-ups of the co-residency fast paths and how many solves each stays paused."""
         g, p = (C.c_int * 4)(), (C.c_int * 4)()
@@ -829,6 +846,48 @@ class AllocatedSolver:
             self.free()
         except Exception:
             pass
+
+
+class Covariance:
+    """What lsq_solver_covariance returns, on the host: `.block(b)` the nb x nb covariance of block b's (local) parameters (a
+    view), `.shared` the ng x ng covariance of a bordered handle's shared parameters (else None), `.stderr` the n standard
+    errors in parameter order (or None), `.info` per block 0 or the 1-based column at which the block's Cholesky failed -- such
+    a block is all NaN (block-diagonal handles only, else None)."""
+
+    def __init__(self, nblocks, nb, ng, cov, stderr=None, info=None):
+        self.nblocks, self.nb, self.ng = int(nblocks), int(nb), int(ng)
+        self.cov = np.asarray(cov, dtype=np.float64)
+        if self.cov.shape != (self.nblocks * self.nb * self.nb + self.ng * self.ng,):
+            raise DimensionMismatch(_lib.EDIM, "covariance of %d blocks of %d parameters and %d shared ones has %d entries, got %s"
+                                    % (self.nblocks, self.nb, self.ng, self.nblocks * self.nb * self.nb + self.ng * self.ng,
+                                       self.cov.shape))
+        self.stderr = None if stderr is None else np.asarray(stderr, dtype=np.float64)
+        if self.stderr is not None and self.stderr.shape != (self.nblocks * self.nb + self.ng,):
+            raise DimensionMismatch(_lib.EDIM, "stderr has shape %s, expected %d values"
+                                    % (self.stderr.shape, self.nblocks * self.nb + self.ng))
+        self.info = None if info is None else np.asarray(info, dtype=np.int32)
+
+    def block(self, b):
+        if not 0 <= b < self.nblocks:
+            raise IndexError("block %d of %d" % (b, self.nblocks))
+        k = self.nb * self.nb
+        return self.cov[b * k:(b + 1) * k].reshape(self.nb, self.nb)
+
+    @property
+    def shared(self):
+        if not self.ng:
+            return None
+        return self.cov[self.nblocks * self.nb * self.nb:].reshape(self.ng, self.ng)
+
+
+def covariance(Jd, f=None, stderr=True):
+    """Covariance of the parameters of a block-diagonal or bordered block-diagonal DeviceMatrix at the values it holds:
+    creates a Cholesky() solver on it, calls AllocatedSolver.covariance and frees the solver."""
+    sv = AllocatedSolver(Jd, Cholesky(), for_lm=True)
+    try:
+        return sv.covariance(f=f, stderr=stderr)
+    finally:
+        sv.free()
 
 
 # ------------------------------------------------------------------------------------------------

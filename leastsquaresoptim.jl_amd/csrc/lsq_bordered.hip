@@ -31,6 +31,7 @@
 
 #include "lsq_solver.h"
 #include "lsq_small64.h"
+#include "lsq_cov.h"
 
 constexpr int BB_R = 32;           // rows per streamed chunk
 constexpr int BB_CS = BB_R + 2;    // column stride of the staged chunk (doubles)
@@ -384,6 +385,124 @@ k_bb_back(int nb, int ng, const double *__restrict__ Uin, const double *__restri
     if (in) x[(size_t)b * nb + lane] = t;
 }
 
+// ---- covariance (lsq_solver_covariance on a bordered handle): s^2 inv(J'J), the B diagonal blocks of the locals and the
+// ng x ng block of the shared parameters.  With the elimination above run WITHOUT damping, S = U_g'U_g is the Schur complement
+// of the locals in J'J and
+//     Cov_gg = s^2 inv(S),      Cov_bb = s^2 X_b X_b' + W_b Cov_gg W_b',   X_b = inv(U_bb),  W_b = X_b U_bg = inv(G_bb) G_bg
+// (the cross blocks -W_b Cov_gg are not formed).  k_bb_eliminate and k_bb_reduce run unchanged; two new kernels follow them in
+// stream order, nothing is exchanged inside a launch, every sum has a fixed association, no floating-point atomics.
+
+// S = sum of the `count` contributions (index order), S = U'U, Cov_gg = s2 inv(U) inv(U)' -> cg (always) and covg / seg (null
+// or the caller's).  One workgroup.
+__global__ void __launch_bounds__(256)
+k_bb_cov_schur(int count, int ng, int col0, int nblocks, const double *__restrict__ contrib, double s2, double *__restrict__ cg,
+               double *__restrict__ covg, double *__restrict__ seg, int *__restrict__ info) {
+    extern __shared__ double bb_lds[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wg = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int NT = (ng + 15) >> 4, ncp = 16 * NT;
+    const int msz = ncp * S64_LS;
+    double *M = bb_lds;
+    double *W = M + msz;
+    int *misc_i = (int *)(W + msz);
+    const int T = ng * (ng + 1) / 2;
+    for (int e = tid; e < ncp * ncp; e += 256) {   // padding: identity; everything the tile products may read is defined
+        const int i = e / ncp, j = e - i * ncp;
+        M[i * S64_LS + j] = (i == j && i >= ng) ? 1.0 : 0.0;
+        W[i * S64_LS + j] = 0.0;
+    }
+    if (tid == 0) misc_i[0] = 0;
+    __syncthreads();
+    const int L = T + ng;
+    for (int e = tid; e < T; e += 256) {
+        double s = 0.0;
+        for (int q = 0; q < count; ++q) s += contrib[(size_t)q * L + e];
+        int i = 0, r = e;
+        while (r >= ng - i) { r -= ng - i; ++i; }
+        M[i * S64_LS + i + r] = s;
+    }
+    __syncthreads();
+    bb_chol_leading<4>(M, W, NT, ncp, &misc_i[0], wg, lane);
+    const int fail = misc_i[0];
+    if (fail) {                                // (the same answer in every thread; a smaller column recorded by k_bb_eliminate stays)
+        if (tid == 0) {
+            atomicMin(&info[0], col0 + fail);
+            atomicMin(&info[1], nblocks);
+        }
+        return;
+    }
+    cov_inv_levels<4>(M, W, NT, wg, lane);
+    for (int t = wg; t < NT * (NT + 1) / 2; t += 4) {
+        int ti = 0, r = t;
+        while (r >= NT - ti) { r -= NT - ti; ++ti; }
+        const int tj = ti + r;
+        const s64_v4d a = cov_tile(W, W, NT, ti, tj, lane);
+        cov_store(cg, nullptr, ng, ti, tj, a, s2, lane);
+        cov_store(covg, seg, ng, ti, tj, a, s2, lane);
+    }
+}
+
+// Cov_bb per block, the geometry of k_bb_eliminate (na = nb + ng > 16: one workgroup per block, else one wavefront per block,
+// four per workgroup).  The rows [U_bb U_bg] of the block are completed to the na x na upper triangular Uh = [U_bb U_bg; 0 I],
+// whose inverse is [X_b -W_b; 0 I]: Y = inv(Uh)' by lsq_cov.h, and with K = diag(s2 I_nb, Cov_gg)
+//     Cov_bb = the leading nb x nb block of Y' K Y.
+// P = K Y differs from s2 Y only in the ng rows of the shared parameters (an ng x nb product, one thread per entry, Cov_gg read
+// from global memory); then the upper tiles of Y'P on the MFMA unit, stored with their mirrors.
+template <int G>
+__global__ void __launch_bounds__(256)
+k_bb_cov_back(int B, int nb, int ng, const double *__restrict__ Uin, const double *__restrict__ cg, double s2,
+              double *__restrict__ cov, double *__restrict__ se) {
+    extern __shared__ double bb_lds[];
+    constexpr int GT = 64 * G;
+    constexpr int TPW = G == 4 ? 3 : 1;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int wg = G == 4 ? __builtin_amdgcn_readfirstlane(wv) : 0;
+    const int gt = G == 4 ? tid : lane;
+    const int b = G == 4 ? (int)blockIdx.x : (int)blockIdx.x * 4 + wv;
+    const bool live = b < B;
+    const int na = nb + ng;
+    const int NT = (na + 15) >> 4, ncp = 16 * NT;
+    const int NTB = (nb + 15) >> 4, nbp = 16 * NTB;    // the tile rows / columns that hold locals
+    const int msz = ncp * S64_LS;
+    double *M = bb_lds + (G == 4 ? 0 : wv) * (size_t)(2 * msz);
+    double *W = M + msz;
+    const double *ub = Uin + (live ? (size_t)b * nb * na : 0);
+    for (int e = gt; e < ncp * ncp; e += GT) {         // Uh (padding, and a workgroup's unused wavefronts: identity)
+        const int k = e / ncp, c = e - k * ncp;
+        double v = k == c ? 1.0 : 0.0;
+        if (live && k < nb && c < na) v = ub[k * na + c];
+        M[k * S64_LS + c] = v;
+        W[k * S64_LS + c] = 0.0;
+    }
+    __syncthreads();
+    cov_diaginv_t<G>(M, W, NT, wg, lane);
+    __syncthreads();
+    cov_inv_levels<G>(M, W, NT, wg, lane);
+    for (int e = gt; e < ncp * nbp; e += GT) {         // P = K Y, the columns of the locals
+        const int k = e / nbp, j = e - k * nbp;
+        double v = 0.0;
+        if (k < nb) v = s2 * W[k * S64_LS + j];
+        else if (k < na)
+            for (int l = 0; l < ng; ++l) v += cg[(k - nb) * ng + l] * W[(nb + l) * S64_LS + j];
+        M[k * S64_LS + j] = v;
+    }
+    __syncthreads();
+    if (!live) return;                                 // (no barrier below)
+    double *cb = cov ? cov + (size_t)b * nb * nb : nullptr;
+    double *sb = se ? se + (size_t)b * nb : nullptr;
+#pragma unroll
+    for (int q = 0; q < TPW; ++q) {
+        const int t = wg + G * q;
+        if (t < NTB * (NTB + 1) / 2) {
+            int ti = 0, r = t;
+            while (r >= NTB - ti) { r -= NTB - ti; ++ti; }
+            const int tj = ti + r;
+            const s64_v4d a = cov_tile(W, M, NT, ti, tj, lane);
+            cov_store(cb, sb, nb, ti, tj, a, 1.0, lane);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
@@ -516,6 +635,80 @@ int lsq_bordered_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const doubl
     if (nmul) *nmul = 1;
     if (st4[1] != INT_MAX) {
         s->last_bd_block = st4[1];
+        lsq_set_error("PosDefException: matrix is not positive definite; Cholesky failed at %d", st4[0]);
+        return LSQ_ENOTPD;
+    }
+    return LSQ_OK;
+}
+
+template <int G>
+static int bb_cov_back(lsq_ctx *c, lsq_solver *s, const double *U, const double *cg, double s2, double *d_cov, double *d_stderr) {
+    const int B = s->br_blocks, na = s->br_nb + s->br_ng;
+    const size_t lds = (G == 4 ? 1 : 4) * 2 * (size_t)(16 * ((na + 15) / 16)) * S64_LS * sizeof(double);
+    LSQ_TRY(lsq_set_lds(c, (const void *)k_bb_cov_back<G>, lds));
+    const int grid = G == 4 ? B : (B + 3) / 4;
+    LSQ_LAUNCH((k_bb_cov_back<G>), dim3(grid), dim3(256), lds, c->stream, B, s->br_nb, s->br_ng, U, cg, s2, d_cov, d_stderr);
+    LSQ_HIP(hipGetLastError());
+    return LSQ_OK;
+}
+
+// lsq_solver_covariance on a bordered handle: d_cov = B nb x nb blocks, then ng x ng; d_stderr = n
+int lsq_bordered_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double *d_cov, double *d_stderr, int *h_info) {
+    lsq_ctx *c = s->ctx;
+    if (J->kind != LSQ_MAT_CSC || J->br_blocks != s->br_blocks || J->br_mb != s->br_mb || J->br_nb != s->br_nb ||
+        J->br_ng != s->br_ng || J->m != s->m || J->n != s->n) {
+        lsq_set_error("lsq_solver_covariance: this solver was allocated for a bordered block-diagonal Jacobian of %d blocks of "
+                      "%d x %d with %d shared columns", s->br_blocks, s->br_mb, s->br_nb, s->br_ng);
+        return LSQ_EARG;
+    }
+    if (d_f && s->m <= s->n) {
+        lsq_set_error("lsq_solver_covariance: the residual variance sum(f.^2) / (m - n) needs m > n (got m = %d, n = %d); "
+                      "pass d_f = NULL for the unscaled inv(J'J)", s->m, s->n);
+        return LSQ_EARG;
+    }
+    LSQ_HIP(hipSetDevice(c->device));
+    LSQ_TRY(lsq_ensure_csc(J));        // (a device-side g! may have written the product mirrors only)
+    const int B = s->br_blocks, nb = s->br_nb, ng = s->br_ng, na = nb + ng;
+    const size_t nz = (size_t)s->m > (size_t)B * nb ? (size_t)s->m : (size_t)B * nb;      // zeros: damping (B nb) and right-hand side (m)
+    if (!s->d_cov_buf) {
+        LSQ_HIP(hipMalloc(&s->d_cov_buf, (nz + (size_t)ng * ng) * sizeof(double)));
+        LSQ_HIP(hipMemsetAsync(s->d_cov_buf, 0, nz * sizeof(double), c->stream));
+    }
+    const double *zero = s->d_cov_buf;
+    double *cg = s->d_cov_buf + nz;
+    double s2 = 1.0;
+    if (d_f) {                         // the library's deterministic reduction (block partials in a fixed order)
+        double ssq = 0.0;
+        LSQ_TRY(lsq_sumsq(c, s->m, d_f, &ssq));
+        s2 = ssq / (double)(s->m - s->n);
+    }
+    const size_t L = bb_contrib_len(ng);
+    double *U = s->d_work, *z = U + (size_t)B * nb * na, *contrib = z + (size_t)B * nb, *partial = contrib + (size_t)B * L;
+    LSQ_LAUNCH(k_bb_init, dim3(1), dim3(64), 0, c->stream, s->d_info);
+    if (na > 16) LSQ_TRY(bb_eliminate<4>(c, s, J, zero, zero, U, z, contrib));
+    else LSQ_TRY(bb_eliminate<1>(c, s, J, zero, zero, U, z, contrib));
+    int count = B;
+    const double *src = contrib;
+    if (B > BB_GS) {
+        count = (B + BB_GS - 1) / BB_GS;
+        LSQ_LAUNCH(k_bb_reduce, dim3((unsigned)((L + 255) / 256), (unsigned)count), dim3(256), 0, c->stream, B, (int)L,
+                   (const double *)contrib, partial);
+        src = partial;
+    }
+    const size_t lds2 = (2 * (size_t)(16 * ((ng + 15) / 16)) * S64_LS + 8) * sizeof(double);
+    LSQ_TRY(lsq_set_lds(c, (const void *)k_bb_cov_schur, lds2));
+    LSQ_LAUNCH(k_bb_cov_schur, dim3(1), dim3(256), lds2, c->stream, count, ng, B * nb, B, src, s2, cg,
+               d_cov ? d_cov + (size_t)B * nb * nb : nullptr, d_stderr ? d_stderr + (size_t)B * nb : nullptr, s->d_info);
+    if (na > 16) LSQ_TRY(bb_cov_back<4>(c, s, U, cg, s2, d_cov, d_stderr));
+    else LSQ_TRY(bb_cov_back<1>(c, s, U, cg, s2, d_cov, d_stderr));
+    s->last_bd_path = 4;
+    s->last_bd_block = -1;
+    int st4[4] = {0, 0, 0, 0};
+    LSQ_TRY(lsq_read_ints(c, s->d_info, s->d_info + 1, nullptr, nullptr, st4));
+    if (h_info) h_info[0] = 0;
+    if (st4[1] != INT_MAX) {
+        s->last_bd_block = st4[1];
+        if (h_info) h_info[0] = st4[0];
         lsq_set_error("PosDefException: matrix is not positive definite; Cholesky failed at %d", st4[0]);
         return LSQ_ENOTPD;
     }

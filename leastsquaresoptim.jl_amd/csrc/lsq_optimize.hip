@@ -56,6 +56,7 @@ extern "C" int lsq_solver_destroy(lsq_solver *s) {
     hipStreamSynchronize(s->ctx->stream);
     if (s->kind == LSQ_LSMR) lsq_lsmr_free(s);
     else lsq_dense_solver_free(s);     // (also the block-diagonal solvers: all they own is d_info, freed there)
+    hipFree(s->d_cov_info); hipFree(s->d_cov_buf);     // lsq_solver_covariance
     delete s;
     return LSQ_OK;
 }

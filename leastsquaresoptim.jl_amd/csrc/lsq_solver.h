@@ -126,6 +126,10 @@ struct lsq_solver {
     // --- Cholesky() on a bordered block-diagonal Jacobian (lsq_bordered.hip): br_blocks > 0; d_info and d_work (the factor rows,
     // the Schur contributions and their partial sums) are allocated ---
     int br_blocks = 0, br_mb = 0, br_nb = 0, br_ng = 0;
+    // --- lsq_solver_covariance on either (lsq_cov.hip, lsq_bordered.hip), allocated on first use: the per-block verdicts;
+    // bordered: zeros (the damping and right-hand side of the elimination) followed by the ng x ng block of the shared parameters
+    int *d_cov_info = nullptr;
+    double *d_cov_buf = nullptr;
 };
 int lsq_tri_chol_solve(lsq_solver *s, const double *U, int n, double *d_bx);
 int lsq_tri_chol_fwd_operands(lsq_solver *s, int n, double **z, unsigned long long **slot, unsigned long long *epoch, int **err);
@@ -241,6 +245,7 @@ int lsq_blockdiag_solve_blocks(lsq_ctx *c, lsq_mat *J, bool pivot, const double 
 // implemented in lsq_bordered.hip
 int lsq_bordered_solver_alloc(lsq_solver *s, const lsq_mat *J);
 int lsq_bordered_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);
+int lsq_bordered_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double *d_cov, double *d_stderr, int *h_info);
 // implemented in lsq_blockqr.hip
 int lsq_blockqr_solver_alloc(lsq_solver *s, const lsq_mat *J);
 int lsq_blockqr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);

@@ -16,6 +16,10 @@
                                                8 B mb (nb+ng+1) bytes at 6.3 TB/s, and LM to convergence on the device tanh model
                                                against LevenbergMarquardt(LSMR()) on the same handle (the only way to solve the
                                                problem on the device without this solver)
+    python tools/blockdiag_bench.py cov        lsq_solver_covariance (lsq_cov.hip, lsq_bordered.hip): B=4096, mb=256, nb = 16, 32, 64
+                                               and bordered (nb, ng) = (8, 8), (32, 16) -- median of 20 after 3 warm-ups, against
+                                               Cholesky()'s lsq_ldiv_damped on the same handle in the same run and against the
+                                               HBM floor 8 B mb (nb+ng) read + 8 (B nb^2 + ng^2) written at 6.3 TB/s
     python tools/blockdiag_bench.py all        (dense, roofline, lm, qr)
     python tools/blockdiag_bench.py lm --batched   one trust region per block (lsq_optimize_batched) against the stacked loop on
                                                the heterogeneous tanh problem (block b starts from 0.3 (b mod 4) (+1, -1, ..),
@@ -262,9 +266,52 @@ def bench_batched(ctx, reps):
         pr.close()
 
 
+def time_call(ctx, fn, reps, warmup=3):
+    evs = HipEvents(ctx)
+    ev = []
+    for k in range(warmup + reps):
+        ctx.sync()
+        evs.start()
+        fn()
+        sec = evs.stop()
+        if k >= warmup:
+            ev.append(sec)
+    return {"event_median_s": statistics.median(ev), "event_min_s": min(ev), "reps": reps}
+
+
+def bench_cov(ctx, reps):
+    """lsq_solver_covariance against Cholesky()'s lsq_ldiv_damped on the same handle in the same run, and against the HBM floor
+    (values read once, covariance written once) at 6.3 TB/s.  Outputs stay on the device (the C entry point, no download)."""
+    B, mb = 4096, 256
+    L = lsq.lib()
+    for nb, ng in ((16, 0), (32, 0), (64, 0), (8, 8), (32, 16)):
+        m, n = B * mb, B * nb + ng
+        if ng:
+            J = lsq.BorderedBlockDiagonal(B, mb, nb, ng, data=lsq.synthetic.bordered_inputs(B, mb, nb, ng, 6))
+        else:
+            J = lsq.BlockDiagonal(B, mb, nb, data=lsq.synthetic.blockdiag_inputs(B, mb, nb, 6))
+        floor_bytes = 8.0 * B * mb * (nb + ng) + 8.0 * (B * nb * nb + ng * ng)
+        out = {"bench": "covariance", "B": B, "mb": mb, "nb": nb, "ng": ng, "floor_bytes": floor_bytes,
+               "floor_s_at_6.3TBs": floor_bytes / (ACHIEVABLE_TBS * 1e12)}
+        Jd = lsq.DeviceMatrix(ctx, J)
+        rng = np.random.default_rng(7)
+        sv = lsq.AllocatedSolver(Jd, lsq.Cholesky(), for_lm=True)
+        dx, dy = lsq.DeviceVector(ctx, n), lsq.DeviceVector(ctx, m, rng.standard_normal(m))
+        dd = lsq.DeviceVector(ctx, n, 0.05 + rng.random(n))
+        dcov, dse = lsq.DeviceVector(ctx, B * nb * nb + ng * ng), lsq.DeviceVector(ctx, n)
+        out["ldiv_damped"] = time_solve(ctx, sv, dx, dy, dd, reps)
+        for name, f in (("covariance", None), ("covariance_with_f", dy.ptr)):
+            out[name] = time_call(ctx, lambda: lsq._lib.check(L.lsq_solver_covariance(sv.h, Jd.h, f, dcov.ptr, dse.ptr, None)), reps)
+            out[name + "_over_ldiv_damped"] = out[name]["event_median_s"] / out["ldiv_damped"]["event_median_s"]
+            out[name + "_over_floor"] = out[name]["event_median_s"] / out["floor_s_at_6.3TBs"]
+        print(json.dumps(out))
+        sv.free()
+        Jd.free()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["dense", "roofline", "lm", "qr", "bordered", "all"])
+    ap.add_argument("what", choices=["dense", "roofline", "lm", "qr", "bordered", "cov", "all"])
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--batched", action="store_true", help="the per-block trust-region loop against the stacked one (only this leg)")
     a = ap.parse_args()
@@ -274,6 +321,9 @@ def main():
         return
     if a.what == "bordered":
         bench_bordered(ctx, max(a.reps, 10))
+        return
+    if a.what == "cov":
+        bench_cov(ctx, max(a.reps, 10))
         return
     if a.what in ("dense", "all"):
         bench_dense(ctx, max(a.reps, 10))
