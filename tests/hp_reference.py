@@ -1,0 +1,148 @@
+"""The accuracy tier's reference: the direct solves in numpy.longdouble (64-bit mantissa on x86-64, eps = 2^-63 = 1.08e-19:
+three to four decimal digits beyond fp64), so that fp64 LAPACK's own error on an operand can be MEASURED and the device held
+to a multiple of it (tests/accuracy_common.py, tests/test_h_gpu_accuracy.py).
+
+Plain numpy: vector operations per column / row, no Python loop over entries.  Inputs are fp64 arrays (converted exactly) or
+longdouble arrays (taken as they are: a column-scaled operand V diag(s) is formed in longdouble by the caller and passed in).
+Every result is longdouble.
+
+    normal_solve(A, y, damp)       (A'A + diag(damp)) x = A'y by an unblocked Cholesky and two triangular solves
+    arrowhead_solve(J, y, damp)    the same equations for a BorderedBlockDiagonal: eliminate per block, Schur complement,
+                                   back-substitute (the algebra of block_solve in tests/test_f_gpu_bordered.py)
+    inv_gram(A)                    inv(A'A) from the Cholesky factor; for a BorderedBlockDiagonal the B local diagonal blocks
+                                   and the shared block of inv(J'J)
+    lstsq_qr(A, y)                 min ||A x - y|| by Householder QR (no pivoting: full column rank is the caller's promise)
+"""
+import numpy as np
+
+LD = np.longdouble
+EPS_LD = float(np.finfo(LD).eps)          # 2^-63 where long double is the x87 format
+
+
+def ld(a):
+    return np.asarray(a).astype(LD)
+
+
+def cholesky_upper(G):
+    """U upper triangular with U'U = G (the upper triangle of G is read).  Left-looking, one row of U per step."""
+    G = ld(G)
+    n = G.shape[0]
+    U = np.zeros((n, n), dtype=LD)
+    for j in range(n):
+        v = G[j, j:] - U[:j, j] @ U[:j, j:]
+        if not v[0] > 0:
+            raise np.linalg.LinAlgError("longdouble Cholesky: pivot %d is not positive" % j)
+        U[j, j:] = v / np.sqrt(v[0])
+    return U
+
+
+def solve_upper(U, b):
+    """x with U x = b; b a vector or a matrix of right-hand sides."""
+    x = ld(b).copy()
+    for i in range(U.shape[0] - 1, -1, -1):
+        x[i] = (x[i] - U[i, i + 1:] @ x[i + 1:]) / U[i, i]
+    return x
+
+
+def solve_upper_t(U, b):
+    """x with U'x = b."""
+    x = ld(b).copy()
+    for i in range(U.shape[0]):
+        x[i] = (x[i] - U[:i, i] @ x[:i]) / U[i, i]
+    return x
+
+
+def chol_solve(U, b):
+    return solve_upper(U, solve_upper_t(U, b))
+
+
+def gram(A, damp=None):
+    A = ld(A)
+    G = A.T @ A
+    if damp is not None:
+        G = G + np.diag(ld(damp))
+    return G
+
+
+def normal_solve(A, y, damp=None):
+    A = ld(A)
+    return chol_solve(cholesky_upper(gram(A, damp)), A.T @ ld(y))
+
+
+def _inv_from_factor(U):
+    Ui = solve_upper(U, np.eye(U.shape[0], dtype=LD))          # inv(U), upper triangular
+    return Ui @ Ui.T
+
+
+def _is_bordered(J):
+    return hasattr(J, "border_block")
+
+
+def arrowhead_parts(J, damp=None, colscale=None):
+    """Per block (G_b, E_b, A_b, C_b) and the shared S0 = C'C (+ damping) of a BorderedBlockDiagonal, in longdouble.
+    colscale: n factors s (the effective Jacobian is J diag(s), formed here without rounding to fp64)."""
+    B, nb, ng = J.nblocks, J.nb, J.ng
+    s = None if colscale is None else ld(colscale)
+    d = None if damp is None else ld(damp)
+    blocks = []
+    S0 = np.zeros((ng, ng), dtype=LD)
+    for b in range(B):
+        A, Cb = ld(J.block(b)), ld(J.border_block(b))
+        if s is not None:
+            A, Cb = A * s[b * nb:(b + 1) * nb], Cb * s[B * nb:]
+        G = A.T @ A
+        if d is not None:
+            G = G + np.diag(d[b * nb:(b + 1) * nb])
+        blocks.append((G, A.T @ Cb, A, Cb))
+        S0 = S0 + Cb.T @ Cb
+    if d is not None:
+        S0 = S0 + np.diag(d[B * nb:])
+    return blocks, S0
+
+
+def arrowhead_solve(J, y, damp=None, colscale=None):
+    B, mb, nb, ng = J.nblocks, J.mb, J.nb, J.ng
+    y = ld(y)
+    blocks, S = arrowhead_parts(J, damp, colscale)
+    rg = np.zeros(ng, dtype=LD)
+    keep = []
+    for b, (G, E, A, Cb) in enumerate(blocks):
+        yb = y[b * mb:(b + 1) * mb]
+        W = chol_solve(cholesky_upper(G), np.column_stack([E, A.T @ yb]))      # inv(G) [A'C_b, A'y_b]
+        S = S - E.T @ W[:, :ng]
+        rg = rg + Cb.T @ yb - E.T @ W[:, ng]
+        keep.append(W)
+    xg = chol_solve(cholesky_upper(S), rg)
+    return np.concatenate([W[:, ng] - W[:, :ng] @ xg for W in keep] + [xg])
+
+
+def inv_gram(A, colscale=None):
+    """inv(A'A) of a dense block; for a BorderedBlockDiagonal: ([local diagonal block b of inv(J'J)], the shared block):
+    with W_b = inv(G_b) E_b and S the Schur complement, shared = inv(S) and local_b = inv(G_b) + W_b inv(S) W_b'."""
+    if not _is_bordered(A):
+        return _inv_from_factor(cholesky_upper(gram(A)))
+    blocks, S = arrowhead_parts(A, None, colscale)
+    Gi, Ws = [], []
+    for G, E, _, _ in blocks:
+        U = cholesky_upper(G)
+        W = chol_solve(U, E)
+        S = S - E.T @ W
+        Gi.append(_inv_from_factor(U))
+        Ws.append(W)
+    Si = _inv_from_factor(cholesky_upper(S))
+    return [Gi[b] + Ws[b] @ Si @ Ws[b].T for b in range(len(blocks))], Si
+
+
+def lstsq_qr(A, y):
+    """Householder QR applied to [A | y], then one back substitution."""
+    R = np.column_stack([ld(A), ld(y)])
+    m, n = R.shape[0], R.shape[1] - 1
+    for j in range(n):
+        v = R[j:, j].copy()
+        alpha = np.sqrt(v @ v)
+        if alpha == 0:
+            raise np.linalg.LinAlgError("longdouble QR: column %d is zero" % j)
+        v[0] += alpha if v[0] >= 0 else -alpha
+        v = v / np.sqrt(v @ v)
+        R[j:, j:] = R[j:, j:] - 2 * np.outer(v, v @ R[j:, j:])
+    return solve_upper(np.triu(R[:n, :n]), R[:n, n])
