@@ -1,5 +1,5 @@
-"""The accuracy tier's operands, metrics and acceptance rule, shared by tests/test_accuracy_host.py (no device) and
-tests/test_h_gpu_accuracy.py.  The reference is tests/hp_reference.py (numpy.longdouble).
+"""The accuracy tier's operands, metrics and acceptance rule, shared by tests/test_accuracy_host.py (no device),
+tests/test_h_gpu_accuracy.py and tests/test_i_gpu_accuracy_*.py.  The reference is tests/hp_reference.py (numpy.longdouble).
 
 Metrics -- all in longdouble, per PIECE (each block; the shared part of a bordered handle separately), so that a small piece
 cannot hide inside a large one:
@@ -7,11 +7,19 @@ cannot hide inside a large one:
                  Invariant under column scaling, as a Cholesky solve is.
     covariance   e(C) = max_ij |C_ij - H_ij| / sqrt(H_ii H_jj);  stderr: max_i |se_i - sqrt(H_ii)| / sqrt(H_ii)
 Rule:
-    e_dev <= 16 * max(e_ref, max(16, k) * 2^-53),  k = unknowns of the piece
+    e_dev <= 16 * max(e_ref, min(max(16, k), 64) * 2^-53),  k = unknowns of the piece
 e_ref is the same metric for fp64 numpy / LAPACK on the same fp64 operand.  The factor 16 is the one
 test_e_gpu_blockqr.py::test_ill_conditioned_blocks uses (another summation order, reciprocals good to 1 ulp); the floor keeps
-a case from failing because LAPACK happened to be exact: k roundings are the natural unit of a length-k accumulation.  The
-bound comes from the reference and that factor, never from what the code under test returns.
+a case from failing because LAPACK happened to be exact: k roundings are the natural unit of a length-k accumulation -- of a
+small piece.  A normwise error over hundreds of unknowns averages, it does not add up (LAPACK's Householder QR stays at 1e-15
+at k = 321), so the floor stops growing at k = 64, the widest piece the block solvers have.  The bound comes from the
+reference and that factor, never from what the code under test returns.
+
+Products (product_bound): every output element i of alpha * A x + beta * y must lie within
+    gamma_(K_i + c) * (|alpha| sum_k |a_ik x_k| + |beta y_i|),   gamma_t = t u / (1 - t u),  u = 2^-53
+of the longdouble value: the standard bound of a length-K_i dot product in ANY summation order, with or without FMA
+(Higham, Accuracy and Stability of Numerical Algorithms, section 3.1), K_i the stored entries that contribute, c <= 8 the further
+roundings counted from the kernel's code.
 
 Operand families (each built per block from a seeded generator):
     plain    the library generator, N(0,1)/sqrt(mb); damping 0.05 + U(0,1)
@@ -19,7 +27,15 @@ Operand families (each built per block from a seeded generator):
              damping 0.1 * colsumabs2, which is what LevenbergMarquardt forms.  Also as a column-scaled handle: V plain, s graded
     ill      U diag(logspace(0, -3, k)) V': cond(G) = 1e6; damping 1e-9 * colsumabs2, or none
     far+/-   plain with operand and y times 2^100 / 2^-100 (damping times 2^200 / 2^-200: the same x)
+
+Dense operands come with two right-hand sides.  random: y standard normal -- a large residual, whose term
+cond^2 u ||r|| / (||A|| ||x||) enters the error of EVERY least-squares solver, a backward-stable QR included.  consistent:
+y = fl(A (z / colnorms)), z standard normal -- a residual at rounding level, where a QR has cond u and anything that squares
+the condition number still cond^2 u: the sharper of the two (tests/test_accuracy_host.py: the fp64 normal equations are 36 to
+41 x beyond the bound there, 19 to 20 x on the random y).
 """
+import functools
+
 import numpy as np
 
 import hp_reference as hp
@@ -28,6 +44,7 @@ import lsq_amd as lsq
 LD = hp.LD
 FACTOR = 16.0
 UNIT = 2.0 ** -53
+FLOOR_CAP = 64                  # the floor max(16, k) 2^-53 stops growing here
 FAMILIES = ("plain", "graded", "ill", "far+", "far-")
 BD_B, BD_MB = 7, 70             # the block-diagonal cases: a grid that ends inside a workgroup of four, two chunks and a ragged third
 BD_NBS = (5, 16, 17, 33, 48, 64)
@@ -39,7 +56,7 @@ def bd_seed(nb):
 
 # ------------------------------------------------------------------------------------------ the rule
 def bound(e_ref, k):
-    return FACTOR * max(float(e_ref), max(16, k) * UNIT)
+    return FACTOR * max(float(e_ref), min(max(16, k), FLOOR_CAP) * UNIT)
 
 
 def accepted(e_dev, e_ref, k):
@@ -165,7 +182,9 @@ def bb_operand(family, B, mb, nb, ng, seed):
     return _finish(family, J, V, s, rng, B * mb, B * nb + ng, make)
 
 
-def dense_operand(family, m, n, seed):
+def dense_operand(family, m, n, seed, rhs="random"):
+    """rhs: "random" or "consistent" (the module docstring); the operand and its damping do not depend on it."""
+    assert rhs in ("random", "consistent")
     rng = np.random.default_rng(seed)
     if family == "ill":
         D = ill_matrix(rng, m, n)
@@ -175,8 +194,163 @@ def dense_operand(family, m, n, seed):
             D = D * grading(n)
     y = rng.standard_normal(m)
     cs = np.sum(D * D, axis=0)
-    damp = {"plain": 0.05 + rng.random(n), "graded": 0.1 * cs, "ill": 1e-9 * cs}[family]
+    damp = (0.1 * cs) if family == "graded" else (1e-9 * cs) if family == "ill" else 0.05 + rng.random(n)
+    if rhs == "consistent":         # (drawn after everything else: the random operand is the one it always was)
+        y = D @ (rng.standard_normal(n) / np.sqrt(cs))
+    if family in ("far+", "far-"):
+        f = 2.0 ** (100 if family == "far+" else -100)
+        D, y, damp = D * f, y * f, damp * f * f
     return Operand(np.asfortranarray(D), y, damp)
+
+
+def stacked(A, y, damp):
+    """[A; diag(sqrt(damp))] and [y; 0] (y a vector or a matrix of right-hand sides), in the dtype of A: the least-squares
+    problem whose normal equations are the damped ones."""
+    n = A.shape[1]
+    zeros = np.zeros((n,) + np.shape(y)[1:], dtype=A.dtype)
+    return np.vstack([A, np.diag(np.sqrt(np.asarray(damp).astype(A.dtype)))]), np.concatenate([np.asarray(y).astype(A.dtype), zeros])
+
+
+def qr_fp64_solve(A, y):
+    """min ||A x - y|| by LAPACK's Householder QR (numpy.linalg.qr) and one triangular solve, all in fp64.  On graded
+    columns it is two to three orders closer to the longdouble solution than numpy.linalg.lstsq (gelsd: an SVD, not invariant
+    under column scaling), so it is the e_ref of the QR cases."""
+    Q, R = np.linalg.qr(A)
+    return np.linalg.solve(R, Q.T @ y)
+
+
+# ------------------------------------------------------------------------------------------ the dense QR cases and their references
+RHS = ("random", "consistent")
+QR_PANEL_SHAPES = [(640, 128), (700, 130), (1000, 321), (400, 256)]
+QR_PANEL_FAMILIES = ("plain", "graded", "ill")
+QR_ROW_VARIANT_MS, QR_ROW_VARIANT_N = [3000, 6000, 12000, 22000], 70
+QR_TSQR_SHAPES = [(33000, 8), (40000, 12), (36000, 16), (40000, 20), (34000, 24), (33000, 28), (40000, 31), (140000, 31)]
+QR_TSQR_FAMILIES = ("plain", "graded", "far+", "far-")
+
+
+def cases(shapes, families):
+    """(m, n, family, rhs, damped), the operand varying slowest: consecutive cases share one cached reference."""
+    return [(m, n, f, r, d) for (m, n) in shapes for f in families for r in RHS for d in (False, True)]
+
+
+def dense_seed(m, n):
+    return 9000 + m + n
+
+
+class QrRef:
+    """One dense operand with both right-hand sides, its longdouble solutions (undamped and damped, computed on first use, one
+    factorisation for both right-hand sides) and the fp64 Householder QR's error on each of the four problems.  far+ / far-
+    take plain's x_hp: scaling operand and y by 2^100 (damping by 2^200) changes no bit of any quotient
+    (tests/test_accuracy_host.py::test_far_operand_has_the_bits_of_plain)."""
+
+    def __init__(self, family, m, n):
+        ops = [dense_operand(family, m, n, dense_seed(m, n), rhs) for rhs in RHS]
+        assert np.array_equal(ops[0].J, ops[1].J)
+        self.family, self.m, self.n = family, m, n
+        self.A, self.damp = ops[0].J, ops[0].damp
+        self.Y = np.column_stack([ops[0].y, ops[1].y])
+        self.S = colnorms(self.A)
+        self._x_hp, self._e_ref = {}, {}
+
+    def problem(self, rhs, damped):
+        """The fp64 least-squares problem of the case: (A, y), stacked if damped."""
+        y = self.Y[:, RHS.index(rhs)]
+        return stacked(self.A, y, self.damp) if damped else (self.A, y)
+
+    def x_hp(self, rhs, damped):
+        if damped not in self._x_hp:
+            if self.family in ("far+", "far-"):
+                self._x_hp[damped] = qr_ref("plain", self.m, self.n).x_hp(None, damped)
+            else:
+                A, Y = hp.ld(self.A), hp.ld(self.Y)
+                if damped:
+                    A, Y = stacked(A, Y, self.damp)
+                self._x_hp[damped] = hp.lstsq_qr(A, Y)
+        X = self._x_hp[damped]
+        return X if rhs is None else X[:, RHS.index(rhs)]
+
+    def err(self, x, rhs, damped):
+        return solve_err(x, self.x_hp(rhs, damped), self.S)
+
+    def e_ref(self, rhs, damped):
+        if (rhs, damped) not in self._e_ref:
+            self._e_ref[rhs, damped] = self.err(qr_fp64_solve(*self.problem(rhs, damped)), rhs, damped)
+        return self._e_ref[rhs, damped]
+
+
+@functools.lru_cache(maxsize=6)
+def qr_ref(family, m, n):
+    return QrRef(family, m, n)
+
+
+# ------------------------------------------------------------------------------------------ products, per output element
+def gamma(t):
+    t = hp.ld(t)
+    return t * LD(UNIT) / (1 - t * LD(UNIT))
+
+
+def product_reference(A, x, alpha, beta, y):
+    """(ref, mag) of alpha * A x + beta * y per output element in longdouble; mag = |alpha| sum_k |a_ik x_k| + |beta y_i|.
+    A: a dense longdouble copy of the effective operand (zeros where nothing is stored)."""
+    A, x, y = hp.ld(A), hp.ld(x), hp.ld(y)
+    a, b = LD(alpha), LD(beta)
+    return a * (A @ x) + b * y, abs(a) * (np.abs(A) @ np.abs(x)) + np.abs(b * y)
+
+
+def product_bound(K, c, mag):
+    """gamma_(K_i + c) * mag_i; K: stored entries per output, c: further roundings (at most 8)."""
+    assert 0 <= c <= 8
+    return gamma(np.asarray(K) + c) * mag
+
+
+def product_excess(out, ref, K, c, mag):
+    """max_i |out_i - ref_i| / bound_i over the outputs with a nonzero bound (elsewhere out must equal ref), and its index."""
+    d = np.abs(hp.ld(out) - ref)
+    b = product_bound(K, c, mag)
+    zero = b == 0
+    if np.any(d[zero] != 0) or not np.all(np.isfinite(d.astype(float))):
+        return np.inf, int(np.argmax(np.where(zero, d, 0)))
+    q = np.where(zero, 0, d / np.where(zero, 1, b))
+    i = int(np.argmax(q))
+    return float(q[i]), i
+
+
+def judge_product(label, out, ref, K, c, mag):
+    q, i = product_excess(out, ref, K, c, mag)
+    print("ACC product %s | %d outputs | worst %d: |err| / bound %.3f (K %d, bound %.3e)"
+          % (label, len(ref), i, q, int(np.asarray(K)[i]), float(product_bound(K, c, mag)[i])))
+    assert q <= 1.0, (label, i, q)
+
+
+def ragged_pattern(m, n, density, seed):
+    """The pattern of tests/test_b_gpu_kernels.py::test_sparse_products: random, one full row (5), an empty column (1) and an
+    empty row (3).  scipy CSC with sorted indices."""
+    import scipy.sparse as sp
+    rng = np.random.default_rng(seed)
+    S = sp.random(m, n, density=density, format="lil", random_state=rng, data_rvs=rng.standard_normal)
+    S[5, :] = rng.standard_normal(n)
+    S[:, 1] = 0
+    S[3, :] = 0
+    S = S.tocsc()
+    S.sort_indices()
+    S.eliminate_zeros()
+    return S
+
+
+def product_scales(m, n, seed):
+    """r (m) and c (n): 12 decades each, shuffled, so that neighbours in a slice, a window or a wavefront differ in scale."""
+    rng = np.random.default_rng(seed)
+    return rng.permutation(grading(m, 12.0)), rng.permutation(grading(n, 12.0))
+
+
+def product_vectors(r, c, seed):
+    """The vectors of the two products of diag(r) S diag(c), balanced so that EVERY stored entry matters to its output and the
+    beta term hides none: J x gets x = z / c (all terms of a row are of the row's size r_i) and is added to y = r * z';
+    J'y gets y = z' / r and is added to x = c * z.  Returns ((x, y) of J x, (y, x) of J'y): (factor, addend) each."""
+    rng = np.random.default_rng(seed)
+    z, zz = rng.standard_normal((2, len(c)))
+    w, ww = rng.standard_normal((2, len(r)))
+    return (z / c, r * w), (ww / r, c * zz)
 
 
 # ------------------------------------------------------------------------------------------ longdouble and fp64 references

@@ -1,6 +1,6 @@
 """The accuracy tier's reference: the direct solves in numpy.longdouble (64-bit mantissa on x86-64, eps = 2^-63 = 1.08e-19:
 three to four decimal digits beyond fp64), so that fp64 LAPACK's own error on an operand can be MEASURED and the device held
-to a multiple of it (tests/accuracy_common.py, tests/test_h_gpu_accuracy.py).
+to a multiple of it (tests/accuracy_common.py, tests/test_h_gpu_accuracy.py, tests/test_i_gpu_accuracy_dense.py).
 
 Plain numpy: vector operations per column / row, no Python loop over entries.  Inputs are fp64 arrays (converted exactly) or
 longdouble arrays (taken as they are: a column-scaled operand V diag(s) is formed in longdouble by the caller and passed in).
@@ -11,7 +11,8 @@ Every result is longdouble.
                                    back-substitute (the algebra of block_solve in tests/test_f_gpu_bordered.py)
     inv_gram(A)                    inv(A'A) from the Cholesky factor; for a BorderedBlockDiagonal the B local diagonal blocks
                                    and the shared block of inv(J'J)
-    lstsq_qr(A, y)                 min ||A x - y|| by Householder QR (no pivoting: full column rank is the caller's promise)
+    lstsq_qr(A, y)                 min ||A x - y|| by Householder QR (no pivoting: full column rank is the caller's promise);
+                                   y may be a matrix of right-hand sides: one factorisation, one solution per column
 """
 import numpy as np
 
@@ -134,15 +135,19 @@ def inv_gram(A, colscale=None):
 
 
 def lstsq_qr(A, y):
-    """Householder QR applied to [A | y], then one back substitution."""
-    R = np.column_stack([ld(A), ld(y)])
-    m, n = R.shape[0], R.shape[1] - 1
+    """Householder QR applied to [A | y], then one back substitution.  y: a vector, or an m x r matrix of right-hand sides
+    (the result is then n x r; every column carries the bits of its own single solve: a reflector is applied column by column).
+    The work array is [A | y] transposed, so that a reflector runs over contiguous memory (tall operands: half the time)."""
+    A = ld(A)
+    m, n = A.shape
+    RT = np.ascontiguousarray(np.column_stack([A, ld(y)]).T)
     for j in range(n):
-        v = R[j:, j].copy()
+        v = RT[j, j:].copy()
         alpha = np.sqrt(v @ v)
         if alpha == 0:
             raise np.linalg.LinAlgError("longdouble QR: column %d is zero" % j)
         v[0] += alpha if v[0] >= 0 else -alpha
         v = v / np.sqrt(v @ v)
-        R[j:, j:] = R[j:, j:] - 2 * np.outer(v, v @ R[j:, j:])
-    return solve_upper(np.triu(R[:n, :n]), R[:n, n])
+        RT[j:, j:] -= 2 * np.outer(RT[j:, j:] @ v, v)
+    R = RT.T
+    return solve_upper(np.triu(R[:n, :n]), R[:n, n] if np.ndim(y) == 1 else R[:n, n:])

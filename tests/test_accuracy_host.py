@@ -9,7 +9,12 @@
 3. The rule separates right from subtly wrong: an fp64 numpy stand-in of the device algorithm (Gram matrix in 32-row chunks
    split four ways, right-looking Cholesky multiplying by a reciprocal square root) passes it on every operand family, and the
    same stand-in with its reciprocal square root rounded through float32 and not corrected fails it on every family -- in
-   every block."""
+   every block.
+4. The dense tier (tests/test_i_gpu_accuracy_dense.py): several right-hand sides in one longdouble factorisation carry the bits
+   of single solves; far operands have plain's solution bit for bit; the reference's residuals on the new operands; a second
+   fp64 Householder QR (rows permuted) passes the rule on EVERY operand of the device tier; the fp64 normal equations do not.
+5. The product bound (tests/test_i_gpu_accuracy_products.py) accepts any summation order and rejects a float32 x and one
+   dropped entry of the smallest row."""
 import numpy as np
 import pytest
 
@@ -225,3 +230,152 @@ def test_rule_floor_and_factor():
     assert ac.bound(0.0, 64) == 16 * 64 * 2.0 ** -53
     assert ac.bound(1e-10, 64) == 16e-10
     assert not ac.accepted(np.nan, 1.0, 5) and not ac.accepted(np.inf, 1.0, 5)
+
+
+def test_rule_floor_is_capped_at_64_unknowns():
+    """Unchanged for every piece of the block solvers (k <= 64); a 321-column norm gets the floor of 64, not of 321."""
+    for k in (1, 5, 16, 17, 33, 48, 63, 64):
+        assert ac.bound(0.0, k) == 16 * max(16, k) * 2.0 ** -53
+        assert ac.bound(3e-13, k) == 16 * 3e-13
+    for k in (65, 70, 129, 200, 321, 384):
+        assert ac.bound(0.0, k) == 16 * 64 * 2.0 ** -53
+    assert ac.accepted(16 * 64 * 2.0 ** -53, 0.0, 321) and not ac.accepted(16 * 65 * 2.0 ** -53, 0.0, 321)
+
+
+# ------------------------------------------------------------------------------------------ 4. the dense tier's reference and rule
+def test_lstsq_qr_multi_rhs_has_the_bits_of_single_solves():
+    for m, n, family in ((700, 130, "graded"), (97, 31, "ill")):
+        ref = ac.qr_ref(family, m, n)
+        for A, Y in ((hp.ld(ref.A), hp.ld(ref.Y)), ac.stacked(hp.ld(ref.A), hp.ld(ref.Y), ref.damp)):
+            X = hp.lstsq_qr(A, Y)
+            assert X.shape == (n, 2) and X.dtype == LD
+            for c in range(2):
+                assert np.array_equal(X[:, c], hp.lstsq_qr(A, Y[:, c]))
+
+
+def test_far_operand_has_the_bits_of_plain():
+    """Operand and y times 2^+-100, damping times 2^+-200: the longdouble solution is plain's bit for bit (what QrRef relies on),
+    and the fp64 operand itself is plain's scaled exactly."""
+    m, n = 300, 20
+    plain = ac.qr_ref("plain", m, n)
+    for family, f in (("far+", 2.0 ** 100), ("far-", 2.0 ** -100)):
+        far = ac.QrRef(family, m, n)
+        assert np.array_equal(far.A, plain.A * f) and np.array_equal(far.Y, plain.Y * f) and np.array_equal(far.damp, plain.damp * f * f)
+        assert np.array_equal(hp.lstsq_qr(far.A, far.Y), plain.x_hp(None, False))
+        assert np.array_equal(hp.lstsq_qr(*ac.stacked(hp.ld(far.A), hp.ld(far.Y), far.damp)), plain.x_hp(None, True))
+        assert np.array_equal(far.S, plain.S * LD(f))
+
+
+@pytest.mark.parametrize("m,n,family", [(700, 130, "plain"), (700, 130, "graded"), (700, 130, "ill"), (33000, 8, "plain"),
+                                        (33000, 8, "graded")])
+def test_lstsq_qr_residual_on_the_dense_tier_operands(m, n, family):
+    """A'(A x - y) = 0 to longdouble level for both right-hand sides, undamped and stacked, column-equilibrated (the scaling a QR
+    solve is invariant under): the bound of test_lstsq_qr_graded_and_stacked_damped."""
+    ref = ac.qr_ref(family, m, n)
+    for damped in (False, True):
+        A, Y = hp.ld(ref.A), hp.ld(ref.Y)
+        if damped:
+            A, Y = ac.stacked(A, Y, ref.damp)
+        S = ac.colnorms(A)
+        As = A / S
+        for c, rhs in enumerate(ac.RHS):
+            x = ref.x_hp(rhs, damped)
+            assert nrm(As.T @ (As @ (S * x) - Y[:, c])) <= 8 * n * LD(2.0) ** -63 * nrm(As) * (nrm(As) * nrm(S * x) + nrm(Y[:, c])), (rhs, damped)
+
+
+def permuted_qr_solve(A, y, seed):
+    """fp64 Householder QR of the row-permuted problem: the same solution, another realisation of LAPACK's rounding errors."""
+    p = np.random.default_rng(seed).permutation(A.shape[0])
+    return ac.qr_fp64_solve(A[p], y[p])
+
+
+QR_OPERANDS = ([(m, n, f) for (m, n) in ac.QR_PANEL_SHAPES for f in ac.QR_PANEL_FAMILIES] +
+               [(m, ac.QR_ROW_VARIANT_N, f) for m in ac.QR_ROW_VARIANT_MS for f in ("graded", "ill")] +
+               [(m, n, f) for (m, n) in ac.QR_TSQR_SHAPES for f in ac.QR_TSQR_FAMILIES])
+
+
+@pytest.mark.parametrize("m,n,family", QR_OPERANDS)
+def test_rule_accepts_another_householder_qr_on_every_dense_operand(m, n, family):
+    """The 'reference alone' condition of the QR groups of tests/test_i_gpu_accuracy_dense.py: on every operand, right-hand side
+    and damping of the device tier a second fp64 Householder QR (rows permuted) passes the rule that the device must pass."""
+    ref = ac.qr_ref(family, m, n)
+    pieces = []
+    for damped in (False, True):
+        for rhs in ac.RHS:
+            x = permuted_qr_solve(*ref.problem(rhs, damped), seed=m + n)
+            pieces.append(("%s %s" % (rhs, "damped" if damped else "undamped"), ref.err(x, rhs, damped), ref.e_ref(rhs, damped), n))
+    ac.judge("permuted QR %dx%d %s" % (m, n, family), pieces)
+
+
+def normal_equations_solve(A, y):
+    return np.linalg.solve(A.T @ A, A.T @ y)
+
+
+@pytest.mark.parametrize("m,n", [(700, 130), (1000, 321)])
+def test_rule_rejects_the_normal_equations_and_the_consistent_rhs_is_the_sharper_one(m, n):
+    """ill (cond 1e3), undamped: a backward-stable QR has an error of cond u, the fp64 normal equations cond^2 u, and the rule
+    must tell them apart.  Consistent y (residual at rounding level): 1.5e-11 against a bound of 3.7e-13 at 700 x 130 (41 x
+    beyond), 2.3e-11 against 6.5e-13 at 1000 x 321 (36 x).  Random y: the residual term cond^2 u ||r|| / (||A|| ||x||) enters the
+    QR's own error as well, e_ref doubles (4.8e-14 against 2.3e-14; 6.3e-14 against 4.1e-14) and the margin halves (19 x, 20 x).
+    The expectation that the random y hides the normal equations altogether did NOT hold on these operands (||x|| ~ 1 / sigma_min
+    keeps the residual term small); what holds, and is asserted, is that the consistent y gives the tighter bound -- which is
+    why the device tier runs both."""
+    ref = ac.qr_ref("ill", m, n)
+    e_ref = {}
+    for rhs in ac.RHS:
+        e = ref.err(normal_equations_solve(*ref.problem(rhs, False)), rhs, False)
+        e_ref[rhs] = ref.e_ref(rhs, False)
+        print("normal equations, %s y: e %.3e, e_ref %.3e, bound %.3e" % (rhs, e, e_ref[rhs], ac.bound(e_ref[rhs], n)))
+        assert not ac.accepted(e, e_ref[rhs], n)
+    assert e_ref["consistent"] < e_ref["random"]
+
+
+# ------------------------------------------------------------------------------------------ 5. the product bound
+def product_case():
+    S = ac.ragged_pattern(500, 40, 0.5, 540)
+    r, c = ac.product_scales(500, 40, 580)
+    (x, y), _ = ac.product_vectors(r, c, 7)
+    return S.toarray() * r[:, None] * c, x, y
+
+
+def pairwise(t):
+    while t.shape[1] > 1:
+        if t.shape[1] % 2:
+            t = np.column_stack([t, np.zeros(t.shape[0])])
+        t = t[:, 0::2] + t[:, 1::2]
+    return t[:, 0]
+
+
+def test_product_bound_accepts_any_summation_order():
+    A, x, y = product_case()
+    K = np.count_nonzero(A, axis=1)
+    ref, mag = ac.product_reference(A, x, 1.5, -0.5, y)
+    assert K[3] == 0 and K[5] == 39 and mag.min() > 0 and float(mag.max() / mag.min()) > 1e10
+    T = A * x                                   # the rounded terms a_ik x_k
+    fwd = np.zeros(500)
+    for k in range(40):
+        fwd = fwd + T[:, k]
+    rev = np.zeros(500)
+    for k in range(39, -1, -1):
+        rev = rev + T[:, k]
+    for name, dot in (("numpy", A @ x), ("forward", fwd), ("reversed", rev), ("pairwise", pairwise(T))):
+        ac.judge_product("host " + name, 1.5 * dot + -0.5 * y, ref, K, 3, mag)
+
+
+def test_product_bound_rejects_a_float32_x_and_a_dropped_entry():
+    A, x, y = product_case()
+    K = np.count_nonzero(A, axis=1)
+    ref, mag = ac.product_reference(A, x, 1.5, -0.5, y)
+    q, _ = ac.product_excess(1.5 * (A @ x.astype(np.float32).astype(np.float64)) - 0.5 * y, ref, K, 3, mag)
+    assert q > 1e3                              # 2^-24 against gamma_43: five orders
+    # one entry of the row with the smallest scale: invisible to a normwise check
+    i = int(np.argmin(np.where(K > 1, np.max(np.abs(A), axis=1), np.inf)))
+    B = A.copy()
+    B[i, np.flatnonzero(A[i])[0]] = 0.0
+    out = 1.5 * (B @ x) - 0.5 * y
+    full = 1.5 * (A @ x) - 0.5 * y
+    assert np.max(np.abs(out - full)) <= 1e-12 * np.max(np.abs(full))          # a whole-vector scale, as the shape tier has it, passes
+    q, worst = ac.product_excess(out, ref, K, 3, mag)
+    assert worst == i and q > 1e3
+    with pytest.raises(AssertionError):
+        ac.judge_product("dropped entry", out, ref, K, 3, mag)

@@ -6,7 +6,7 @@ block, on operands whose Gram matrices have condition numbers below 10: six to s
 reference is numpy.longdouble (tests/hp_reference.py), the error is measured per piece in a scaling-invariant metric, and the
 device must satisfy
 
-    e_dev <= 16 * max(e_ref, max(16, k) * 2^-53)
+    e_dev <= 16 * max(e_ref, min(max(16, k), 64) * 2^-53)
 
 where e_ref is the error of fp64 numpy / LAPACK on the same operand (tests/accuracy_common.py has the metrics, the rule and
 the operand families plain / graded / ill / far; tests/test_accuracy_host.py shows on the CPU that the rule passes an fp64
@@ -194,8 +194,8 @@ def test_dense_qr_panel(ctx, c, monkeypatch):
         assert info["qr_panel"] == "cholqr2"
     x_hp = hp.lstsq_qr(A, y)
     S = ac.colnorms(A)
-    x_ref = np.linalg.lstsq(A, y, rcond=None)[0]
-    ac.judge("dense qr c=%s (%s)" % (c, info["qr_panel"]), [("x", ac.solve_err(x, x_hp, S), ac.solve_err(x_ref, x_hp, S), n)])
+    e_ref = min(ac.solve_err(np.linalg.lstsq(A, y, rcond=None)[0], x_hp, S), ac.solve_err(ac.qr_fp64_solve(A, y), x_hp, S))
+    ac.judge("dense qr c=%s (%s)" % (c, info["qr_panel"]), [("x", ac.solve_err(x, x_hp, S), e_ref, n)])
 
 
 # ------------------------------------------------------------------------------------------ 9. BlockQR(), graded
@@ -221,6 +221,7 @@ def test_blockqr_graded(ctx, mb, nb, damped):
             A64, y64 = np.vstack([A64, np.diag(np.sqrt(db))]), np.concatenate([y64, np.zeros(nb)])
         x_hp = hp.lstsq_qr(A, yb)
         S = ac.colnorms(J.block(b))
-        x_ref = np.linalg.lstsq(A64, y64, rcond=None)[0]
-        pieces.append(("block %d" % b, ac.solve_err(x[b * nb:(b + 1) * nb], x_hp, S), ac.solve_err(x_ref, x_hp, S), nb))
+        # (the better of LAPACK's two: gelsd is not invariant under column scaling and loses two to three digits on graded columns)
+        e_ref = min(ac.solve_err(np.linalg.lstsq(A64, y64, rcond=None)[0], x_hp, S), ac.solve_err(ac.qr_fp64_solve(A64, y64), x_hp, S))
+        pieces.append(("block %d" % b, ac.solve_err(x[b * nb:(b + 1) * nb], x_hp, S), e_ref, nb))
     ac.judge("blockqr graded %dx%d %s" % (mb, nb, "damped" if damped else "undamped"), pieces)
