@@ -281,6 +281,29 @@ int lsq_solver_blockdiag_ranks(const lsq_solver *s, int *h_ranks);
  *   (W_b = inv(J_b'J_b) J_b'C_b) are NOT formed.
  * Synchronises the stream when it has host results to return (h_info, the bordered handle's status); otherwise stream-ordered. */
 int lsq_solver_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double *d_cov, double *d_stderr, int *h_info);
+/* The same for the plain dense J::Matrix of the reference (lsq_dense_create; the handle of LevenbergMarquardt(Cholesky()),
+ * dense_cholesky.jl:43-59, Dogleg(Cholesky()), :29-35, and QR(), dense_qr.jl:30-88): Cov = s^2 inv(J'J) without moving J to
+ * the host.  lsq_solver_covariance keeps refusing dense handles; this is the entry point beside it.  `s` is an LSQ_CHOLESKY
+ * solver created on J, either for_lm (it owns the scratch: the first call allocates 2 n^2 doubles for inv(U) and its
+ * workspace).  A solver of another kind, a handle that is not dense (CSC, block-diagonal, bordered, operator), a shape that
+ * differs from the solver's, or d_cov and d_stderr both NULL: LSQ_EARG with a message in lsq_last_error.  A column-scaled
+ * dense handle means J S.  No damping is involved; J and d_f are not written.
+ *   d_f: NULL (the unscaled inv(J'J)) or the residual (m doubles, device): s^2 = sum(f.^2) / (m - n) through lsq_sumsq, as
+ *   for the bordered handle.  m <= n with d_f: LSQ_EARG.
+ *   d_cov: NULL or n*n doubles, column-major, both triangles written with the same bits.
+ *   d_stderr: NULL or n doubles, s * sqrt(sum_{k >= i} X_ik^2) with X = inv(U), J'J = U'U.  They come from a kernel of their
+ *   own with a fixed summation order: the same bits whether or not d_cov is asked for.  They agree with sqrt(diag(cov)) to
+ *   rounding, NOT bit for bit (the covariance adds the same squares in the matrix unit's order).
+ * J'J = U'U is the unpivoted factorisation of the damped solve with no damping added.  A pivot that is not positive:
+ * LSQ_ENOTPD, the 1-based column at which the unpivoted dpotrf of J'J stops in the message -- the one lsq_ldiv_damped sets --
+ * and in h_info[0] when h_info is given (0 on success); d_cov / d_stderr are then unspecified, and the solver remains usable
+ * for solves and for further covariances.  (A pseudo-inverse for rank-deficient J is not offered, nor a covariance from the
+ * QR() factor, which would not square the condition number.)
+ * The result has the same bits on every run, under lsq_debug_set(serial = 1), and for either for_lm.  lsq_solver_chol_path
+ * afterwards reports the factorisation that was used: 2 or 4 (1 for the few operands that lsq_ldiv_damped, too, keeps in one
+ * workgroup: n < 32 with m * n < 20000, or n = 1).  Waits for the stream once, in the middle -- for the info word and s^2,
+ * which are read back to back; the last two launches are stream-ordered behind that. */
+int lsq_dense_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double *d_cov, double *d_stderr, int *h_info);
 
 /* The fast paths above that rely on co-resident workgroups (one-launch Cholesky, pipelined triangular solves, the QR panel's slab
  * exchange + pipelined certified solve) wait with a bound; a wait that gives up makes the solve repeat itself on the

@@ -829,6 +829,18 @@ class AllocatedSolver:
         check(lib().lsq_solver_covariance(self.h, J.h, _ptr(df), dcov.ptr, _ptr(dse), info.ctypes.data_as(_lib.c_ip)))
         return Covariance(B, nb, ng, dcov.get(), dse.get() if stderr else None, info[:B] if not ng else None)
 
+    def dense_covariance(self, f=None, stderr=True):
+        """lsq_dense_covariance at the values the dense J holds now: a DenseCovariance.  `f`: None (the unscaled inv(J'J)), or
+        the residual there (DeviceVector or m host values): s^2 = sum(f.^2) / (m - n)."""
+        J = self.J
+        df = f if (f is None or hasattr(f, "ptr")) else DeviceVector(J.ctx, J.m, f)
+        n = J.n if not J.sparse else 0       # (any other handle is refused by the library, with its message)
+        dcov = DeviceVector(J.ctx, n * n)
+        dse = DeviceVector(J.ctx, J.n) if stderr else None
+        info = np.zeros(1, dtype=np.int32)
+        check(lib().lsq_dense_covariance(self.h, J.h, _ptr(df), dcov.ptr, _ptr(dse), info.ctypes.data_as(_lib.c_ip)))
+        return DenseCovariance(J.n, dcov.get(), dse.get() if stderr else None)
+
     def stats(self):
         """lsq_solver_stats: give-ups of the co-residency fast paths and how many solves each stays paused."""
         g, p = (C.c_int * 4)(), (C.c_int * 4)()
@@ -886,6 +898,32 @@ def covariance(Jd, f=None, stderr=True):
     sv = AllocatedSolver(Jd, Cholesky(), for_lm=True)
     try:
         return sv.covariance(f=f, stderr=stderr)
+    finally:
+        sv.free()
+
+
+class DenseCovariance:
+    """What lsq_dense_covariance returns, on the host: `.cov` the n x n covariance s^2 inv(J'J) (symmetric to the bit),
+    `.stderr` the n standard errors (or None), `.n` the number of parameters."""
+
+    def __init__(self, n, cov, stderr=None):
+        self.n = int(n)
+        cov = np.asarray(cov, dtype=np.float64)
+        if cov.size != self.n * self.n or cov.ndim > 2 or (cov.ndim == 2 and cov.shape != (self.n, self.n)):
+            raise DimensionMismatch(_lib.EDIM, "covariance of %d parameters has %d x %d entries, got %s"
+                                    % (self.n, self.n, self.n, cov.shape))
+        self.cov = cov.reshape((self.n, self.n), order="F")
+        self.stderr = None if stderr is None else np.asarray(stderr, dtype=np.float64)
+        if self.stderr is not None and self.stderr.shape != (self.n,):
+            raise DimensionMismatch(_lib.EDIM, "stderr has shape %s, expected %d values" % (self.stderr.shape, self.n))
+
+
+def dense_covariance(Jd, f=None, stderr=True):
+    """Covariance of the parameters of a dense DeviceMatrix at the values it holds: creates a Cholesky() solver on it, calls
+    AllocatedSolver.dense_covariance and frees the solver."""
+    sv = AllocatedSolver(Jd, Cholesky(), for_lm=True)
+    try:
+        return sv.dense_covariance(f=f, stderr=stderr)
     finally:
         sv.free()
 

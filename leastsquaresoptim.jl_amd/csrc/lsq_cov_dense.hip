@@ -1,0 +1,193 @@
+// Parameter covariance of a plain dense Jacobian: lsq_dense_covariance, Cov = s^2 inv(J'J), s^2 = sum(f.^2) / (m - n) (or 1).
+//
+// Everything up to the last product exists elsewhere and is only enqueued here:
+//   1. G = J'J and G = U'U: lsq_cholesky_blocked (lsq_dense_mfma.hip: MFMA SYRK, one-launch or panel factorisation), or -- on
+//      the operands lsq_cholesky_solve keeps away from the blocked path -- lsq_cholesky_small_factor (lsq_dense.hip)
+//   2. X = inv(U) into the upper triangle of s->tri_X: lsq_tri_inv_enqueue (lsq_qr.hip: k_tri_diaginv + k_tri_level)
+//   3. k_cov_xxt: inv(G) = X X', one workgroup per 64 x 64 upper tile (I, J), I <= J:  C_IJ = sum_{K >= J} X_IK X_JK'.
+//      Only K >= J contributes (X_JK = 0 for K < J); the diagonal blocks of X are masked below their diagonal on the way into
+//      LDS -- tri_X is never written there, and what it holds may be NaN -- and rows, columns and k's past n likewise.  The K
+//      blocks are added in index order into one set of accumulators: no split over K, no floating-point atomics, the same
+//      bits on every run.  Accumulators times s^2 go to (i, j) and to the mirror (j, i); in a diagonal tile only i <= j is
+//      stored.  Tile column J has nt - J blocks of work, so the tiles are numbered by columns: the long ones start first.
+//   4. k_cov_stderr: s sqrt(sum_{k >= i} X_ik^2), one wavefront per row in a fixed lane-strided order and a fixed butterfly;
+//      a kernel of its own, so that its bits do not depend on whether the covariance was asked for.  It agrees with
+//      sqrt(diag(cov)) to rounding only (the MFMA unit adds the same squares in another order).
+#include <cmath>
+
+#include "lsq_solver.h"
+
+int lsq_cholesky_blocked(lsq_solver *s, lsq_mat *J, const double *d_damp, double *d_x, double *d_dmax, bool allow_tiles,
+                         const double *d_y);   // lsq_dense_mfma.hip
+
+constexpr int CX_T = 64;            // tile
+constexpr int CX_KC = 32;           // k's staged per step
+constexpr int CX_KS = CX_KC + 2;    // LDS row stride (doubles)
+typedef double cx_v4d __attribute__((ext_vector_type(4)));
+
+// wave and fragment layout of k_tri_level (lsq_qr.hip): four wavefronts own the 32 x 32 quadrants, 2 x 2 MFMA 16 x 16 x 4 tiles
+// each; operand A: lane & 15 = row, lane >> 4 = k; operand B: lane & 15 = column; accumulator r: row (lane >> 4) + 4 r
+__global__ void __launch_bounds__(256)
+k_cov_xxt(const double *__restrict__ X, int n, double s2, double *__restrict__ C) {
+    __shared__ double sA[CX_T * CX_KS];
+    __shared__ double sB[CX_T * CX_KS];
+    int t = blockIdx.x, tj = 0;
+    while (t > tj) { t -= tj + 1; ++tj; }      // tile column tj holds tiles ti = 0 .. tj
+    const int ti = t;
+    const int i0 = ti * CX_T, j0 = tj * CX_T;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int wr = (w >> 1) * 32, wc = (w & 1) * 32;
+    cx_v4d acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) acc[a][b] = (cx_v4d){0.0, 0.0, 0.0, 0.0};
+    // staging: lane = row of X (coalesced down a column k), 8 k's per thread; A(m, k) = X(i0 + m, k), B(k, c) = X(j0 + c, k)
+    const int am = tid & 63, akq = (tid >> 6) * 8;
+    const int ia = i0 + am, jb = j0 + am;
+    const bool rows_full = j0 + CX_T <= n;      // (then i0 + 64 <= n as well)
+    double ra[8], rb[8];
+    auto fetch = [&](int k0) {
+        if (rows_full && k0 >= j0 + CX_T && k0 + CX_KC <= n) {   // past both diagonal blocks, inside the matrix: full blocks
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const size_t col = (size_t)(k0 + akq + q) * n;
+                ra[q] = X[col + ia];
+                rb[q] = X[col + jb];
+            }
+        } else {                                // X(r, k) exists for r <= k < n only
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int k = k0 + akq + q;
+                ra[q] = (k < n && ia <= k) ? X[(size_t)k * n + ia] : 0.0;
+                rb[q] = (k < n && jb <= k) ? X[(size_t)k * n + jb] : 0.0;
+            }
+        }
+    };
+    fetch(j0);
+    for (int k0 = j0; k0 < n; k0 += CX_KC) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            sA[am * CX_KS + akq + q] = ra[q];
+            sB[am * CX_KS + akq + q] = rb[q];
+        }
+        __syncthreads();
+        if (k0 + CX_KC < n) fetch(k0 + CX_KC);
+#pragma unroll
+        for (int kk = 0; kk < CX_KC; kk += 4) {
+            const int ko = kk + (lane >> 4);
+            const double a0 = sA[(wr + (lane & 15)) * CX_KS + ko];
+            const double a1 = sA[(wr + 16 + (lane & 15)) * CX_KS + ko];
+            const double b0 = sB[(wc + (lane & 15)) * CX_KS + ko];
+            const double b1 = sB[(wc + 16 + (lane & 15)) * CX_KS + ko];
+            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = i0 + wr + a * 16 + (lane >> 4) + 4 * r;
+                const int col = j0 + wc + b * 16 + (lane & 15);
+                if (row < n && col < n && row <= col) {        // (row <= col: always true off the diagonal tiles)
+                    const double v = s2 * acc[a][b][r];
+                    C[(size_t)col * n + row] = v;
+                    if (row != col) C[(size_t)row * n + col] = v;
+                }
+            }
+}
+
+__global__ void __launch_bounds__(256)
+k_cov_stderr(const double *__restrict__ X, int n, double s, double *__restrict__ se) {
+    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;
+    double acc = 0.0;
+    for (int k = i + lane; k < n; k += 64) {
+        const double x = X[(size_t)k * n + i];
+        acc += x * x;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
+    if (lane == 0) se[i] = s * sqrt(acc);
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------
+// G = J'J = U'U into s->d_chol and X = inv(U) into s->tri_X, enqueued; the factorisation's verdict in s->d_info[0]
+static int factor_and_invert(lsq_solver *s, lsq_mat *J, bool allow_tiles) {
+    const int m = J->m, n = J->n;
+    if (lsq_cholesky_takes_blocked(m, n)) {
+        LSQ_TRY(lsq_cholesky_blocked(s, J, nullptr, nullptr, nullptr, allow_tiles, nullptr));
+        s->last_chol_path = s->last_chol_tiles ? 4 : 2;
+    } else {
+        LSQ_TRY(lsq_cholesky_small_factor(s, J));
+        s->last_chol_path = 1;
+    }
+    return lsq_tri_inv_enqueue(s, s->d_chol, n);
+}
+
+extern "C" int lsq_dense_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double *d_cov, double *d_stderr,
+                                    int *h_info) {
+    LSQ_RANGE("lsq_dense_covariance");
+    if (!s || !J) { lsq_set_error("lsq_dense_covariance: null argument"); return LSQ_EARG; }
+    if (!d_cov && !d_stderr) {
+        lsq_set_error("lsq_dense_covariance: d_cov and d_stderr are both NULL: nothing to compute");
+        return LSQ_EARG;
+    }
+    if (s->kind != LSQ_CHOLESKY || s->bd_blocks != 0 || s->br_blocks != 0 || !s->d_chol) {
+        lsq_set_error("lsq_dense_covariance: needs a Cholesky() solver created on a dense Jacobian (lsq_dense_create); this "
+                      "solver's kind is %d%s", s->kind, (s->bd_blocks || s->br_blocks) ? ", on a block-diagonal handle" : "");
+        return LSQ_EARG;
+    }
+    if (J->kind != LSQ_MAT_DENSE) {
+        lsq_set_error("lsq_dense_covariance: the Jacobian is not a dense handle (lsq_dense_create); block-diagonal and bordered "
+                      "handles have lsq_solver_covariance, CSC and operator handles are not offered");
+        return LSQ_EARG;
+    }
+    if (J->m != s->m || J->n != s->n) {
+        lsq_set_error("lsq_dense_covariance: this solver was allocated for a %d x %d Jacobian, got %d x %d", s->m, s->n, J->m, J->n);
+        return LSQ_EARG;
+    }
+    const int m = J->m, n = J->n;
+    if (d_f && m <= n) {
+        lsq_set_error("lsq_dense_covariance: the residual variance sum(f.^2) / (m - n) needs m > n (got m = %d, n = %d); "
+                      "pass d_f = NULL for the unscaled inv(J'J)", m, n);
+        return LSQ_EARG;
+    }
+    if (h_info) h_info[0] = 0;
+    if (n <= 0) return LSQ_OK;
+    lsq_ctx *c = s->ctx;
+    LSQ_HIP(hipSetDevice(c->device));
+    double ssq = 0.0;
+    int st4[4] = {0, 0, 0, 0};
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        LSQ_TRY(factor_and_invert(s, J, attempt == 0));
+        // the one wait of the call: the variance (on the first round) and the factorisation's verdict behind it
+        if (d_f && attempt == 0) LSQ_TRY(lsq_sumsq(c, m, d_f, &ssq));
+        LSQ_TRY(lsq_read_ints(c, s->d_info, nullptr, nullptr, nullptr, st4));
+        if (st4[0] != -1 || s->fb_tiles.off()) break;
+        s->fb_tiles.gave_up(c, LSQ_FB_CHOL_TILES);     // the one-launch factorisation gave up on a wait: panel launches, once more
+    }
+    s->fb_tiles.solve_done(s->last_chol_path == 4);
+    const int info = st4[0];
+    if (info != 0) {
+        if (h_info) h_info[0] = info;
+        lsq_set_error("PosDefException: matrix is not positive definite; Cholesky failed at %d", info);
+        return LSQ_ENOTPD;
+    }
+    const double s2 = d_f ? ssq / (double)(m - n) : 1.0;
+    if (d_cov) {
+        const int nt = lsq_div_up(n, CX_T);
+        LSQ_LAUNCH(k_cov_xxt, dim3(nt * (nt + 1) / 2), dim3(256), 0, c->stream, (const double *)s->tri_X, n, s2, d_cov);
+    }
+    if (d_stderr) LSQ_LAUNCH(k_cov_stderr, dim3(lsq_div_up(n, 4)), dim3(256), 0, c->stream, (const double *)s->tri_X, n, sqrt(s2), d_stderr);
+    LSQ_HIP(hipGetLastError());
+    return LSQ_OK;
+}

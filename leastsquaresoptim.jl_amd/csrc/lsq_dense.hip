@@ -340,6 +340,24 @@ static bool chol_certified(lsq_solver *s, lsq_mat *J, const double *d_y, double 
     return true;
 }
 
+// which operands lsq_cholesky_solve sends to the blocked path (the others: the one-workgroup kernels)
+bool lsq_cholesky_takes_blocked(int m, int n) { return n >= 32 || (n >= 2 && (long long)m * n >= 20000); }
+
+// the one-workgroup path without a right-hand side (lsq_dense_covariance on the operands the blocked path never sees):
+// J'J by k_syrk_upper, the unpivoted dpotf2 of k_chol_solve<false> on it (its solve runs on zeros).  U in s->d_chol,
+// 0 or the failing column in s->d_info[0]; stream-ordered
+int lsq_cholesky_small_factor(lsq_solver *s, lsq_mat *J) {
+    lsq_ctx *c = s->ctx;
+    const int m = J->m, n = J->n;
+    const int nt = (n + SY_T - 1) / SY_T;
+    LSQ_LAUNCH(k_syrk_upper, dim3(nt * (nt + 1) / 2), dim3(256), 0, c->stream, J->d_dense, m, n, s->d_chol, (const double *)nullptr);
+    LSQ_HIP(hipMemsetAsync(s->d_rhs, 0, (size_t)n * sizeof(double), c->stream));
+    LSQ_LAUNCH((k_chol_solve<false>), dim3(1), dim3(CH_NT), 0, c->stream, s->d_chol, n, s->d_rhs, s->d_info, (int *)s->d_tau,
+               s->d_work, s->d_work + 2 * n);
+    LSQ_HIP(hipGetLastError());
+    return LSQ_OK;
+}
+
 // dense_cholesky.jl:29-35 (d_damp == nullptr: pivoted) and :43-59 (damped, unpivoted)
 int lsq_cholesky_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul) {
     lsq_ctx *c = s->ctx;
@@ -352,7 +370,7 @@ int lsq_cholesky_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const doubl
     int rc_cert = LSQ_OK;
     // blocked path from n = 32, or earlier when the rows make the SYRK the whole cost (tall and thin: 10^6 x 20 takes
     // 1.8 ms blocked, 90 ms with the one-workgroup kernels; 300 x 8 0.15 vs 0.09)
-    const bool blocked = n >= 32 || (n >= 2 && (long long)m * n >= 20000);
+    const bool blocked = lsq_cholesky_takes_blocked(m, n);
     if (blocked && d_damp) {
         // MFMA SYRK + blocked Cholesky + pipelined solves (lsq_dense_mfma.hip); measured crossover against the
         // single-workgroup kernel: 200 x 16 0.15 vs 0.11 ms, 300 x 32 0.15 vs 0.18, 500 x 64 0.16 vs 0.32, 2000 x 127 0.24 vs 0.93

@@ -1257,11 +1257,11 @@ void lsq_tri_pipe_disable(lsq_solver *s) {
     s->fb_pipe.gave_up(s->ctx, LSQ_FB_TRI_PIPE);
 }
 
-// sum of squares of inv(U) for the n x n upper triangle U (explicit inverse: k_tri_diaginv + k_tri_level levels);
-// synchronises the stream.  NaN / Inf when U is singular.
-int lsq_tri_inv_fro2(lsq_solver *s, const double *U, int n, double *fro2_inv) {
+constexpr int FRO_BLOCKS = 256;
+// X = inv(U) into the upper triangle of s->tri_X (column-major, ld n) for the n x n upper triangle U: k_tri_diaginv + the
+// k_tri_level levels, enqueued on the stream, no synchronisation.  Below the diagonal blocks tri_X is never written.
+int lsq_tri_inv_enqueue(lsq_solver *s, const double *U, int n) {
     lsq_ctx *c = s->ctx;
-    constexpr int FRO_BLOCKS = 256;
     if (!s->tri_X) {
         LSQ_HIP(hipMalloc(&s->tri_X, ((size_t)n * n + 8) * sizeof(double)));
         LSQ_HIP(hipMalloc(&s->tri_T, ((size_t)n * n + 8) * sizeof(double)));
@@ -1275,6 +1275,14 @@ int lsq_tri_inv_fro2(lsq_solver *s, const double *U, int n, double *fro2_inv) {
         LSQ_LAUNCH(k_tri_level, dim3(grid), dim3(256), 0, c->stream, U, s->tri_X, s->tri_T, n, sb, 0);
         LSQ_LAUNCH(k_tri_level, dim3(grid), dim3(256), 0, c->stream, U, s->tri_X, s->tri_T, n, sb, 1);
     }
+    return LSQ_OK;
+}
+
+// sum of squares of inv(U) for the n x n upper triangle U (explicit inverse: lsq_tri_inv_enqueue);
+// synchronises the stream.  NaN / Inf when U is singular.
+int lsq_tri_inv_fro2(lsq_solver *s, const double *U, int n, double *fro2_inv) {
+    lsq_ctx *c = s->ctx;
+    LSQ_TRY(lsq_tri_inv_enqueue(s, U, n));
     LSQ_LAUNCH(k_tri_fro, dim3(FRO_BLOCKS), dim3(256), 0, c->stream, U, s->tri_X, n, s->tri_fro);
     LSQ_HIP(hipMemcpyAsync(s->tri_hfro, s->tri_fro, 2 * FRO_BLOCKS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     LSQ_HIP(hipStreamSynchronize(c->stream));

@@ -237,6 +237,10 @@ int lsq_dense_solver_alloc(lsq_solver *s);
 void lsq_dense_solver_free(lsq_solver *s);
 int lsq_cholesky_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);
 int lsq_qr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);
+bool lsq_cholesky_takes_blocked(int m, int n);
+int lsq_cholesky_small_factor(lsq_solver *s, lsq_mat *J);
+// implemented in lsq_qr.hip: X = inv(U) into the upper triangle of s->tri_X (stream-ordered; tri_X / tri_T allocated on first use)
+int lsq_tri_inv_enqueue(lsq_solver *s, const double *U, int n);
 // implemented in lsq_blockdiag.hip
 int lsq_blockdiag_solver_alloc(lsq_solver *s, const lsq_mat *J);
 int lsq_blockdiag_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);
