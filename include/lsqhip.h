@@ -247,8 +247,8 @@ int lsq_solver_qr_panel(const lsq_solver *s, int *kind);
 /* the same for Cholesky() (dense_cholesky.jl:29-59):  0 none yet, 1 one-workgroup kernel (dpotf2 / pivoted dpstf2),
  * 2 blocked unpivoted factorisation (LM: J'J + damp),  3 blocked unpivoted factorisation + full-rank certificate
  * (Dogleg: 1 / ||inv(U)||_F^2 > 16 n eps max diag proves that cholesky!(.., Val(true)) would not stop early),
- * 4 like 2 with the whole factorisation in ONE launch (k_chol_tiles: one resident workgroup per 64 x 64 upper tile,
- * n <= 1408; repeated as 2 if one of its bounded waits gives up) */
+ * 4 like 2 with the whole factorisation in ONE launch (k_chol_chain: one resident workgroup per 64 x 64 upper tile
+ * and one for the diagonal chain, n <= 1408; repeated as 2 if one of its bounded waits gives up) */
 int lsq_solver_chol_path(const lsq_solver *s, int *path);
 /* diagnostics of the last block solve: which path (0 none yet, 1 batched unpivoted LM, 2 batched pivoted Dogleg, 3 batched
  * per-block pivoted QR: LSQ_BLOCK_QR, block = -1, 4 bordered Schur, LM: lsq_blockdiag_bordered_create) and, after LSQ_ENOTPD /
@@ -309,7 +309,7 @@ int lsq_dense_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double *d
  * exchange + pipelined certified solve) wait with a bound; a wait that gives up makes the solve repeat itself on the
  * launch-per-step path, is COUNTED, and pauses that fast path for a number of solves (16, then 64, ... up to 4096 while it
  * keeps failing right after being armed again; back to 16 after a clean run) instead of switching it off for good: a
- * neighbour on the device (an RCCL kernel of a sharded run) may be gone by then.  Index: 0 one-launch Cholesky (k_chol_tiles),
+ * neighbour on the device (an RCCL kernel of a sharded run) may be gone by then.  Index: 0 one-launch Cholesky (k_chol_chain),
  * 1 pipelined triangular solves, 2 QR slab exchange / pipelined certified solve, 3 CholeskyQR2 panel breakdowns (numerical:
  * ill-conditioned panels -- counted and paused the same way).  h_giveups: totals of this solver; h_paused: solves left before
  * the path is tried again (0 = armed).  Either pointer may be NULL. */

@@ -181,7 +181,7 @@ static inline bool lsq_prof_take(lsq_ctx *c, hipEvent_t *start, hipEvent_t *stop
 // sparse / dense matrix handle
 // ---------------------------------------------------------------------------------------------
 enum { LSQ_MAT_DENSE = 0, LSQ_MAT_CSC = 1, LSQ_MAT_OP = 2 };
-enum { LSQ_PLAN_STREAM = 0, LSQ_PLAN_WAVE = 1, LSQ_PLAN_BLOCK = 2, LSQ_PLAN_LDSWIN = 3 };
+enum { LSQ_PLAN_STREAM = 0, LSQ_PLAN_WAVE = 1, LSQ_PLAN_BLOCK = 2 };
 
 // One direction of a sparse product: segments (rows for J*x via the CSR mirror, columns for
 // J'*y via CSC) with the launch plan chosen once per pattern from the segment-length profile.
@@ -196,12 +196,11 @@ struct LsqSegs {
     int plan = LSQ_PLAN_STREAM;
     int ntiles = 0;        // stream plan: number of tiles
     int *d_tiles = nullptr; // ntiles+1 segment boundaries of the tiles
-    int *d_order = nullptr; // optional permutation of the work items (XCD-aware placement)
     int nx = 0;            // length of the gathered vector (n for CSR rows, m for CSC columns)
     int rw = 0;            // window-blocked CSC: rows per window
     int nwin = 0;          // window-blocked CSC: number of windows (segments = nwin * n)
-    int *d_wtile = nullptr; // LDS-window plan: nwin+1 big-tile ranges of the windows
-    int nbig = 0;          // stream plan, LDS-staged variant: number of big tiles
+    int *d_wtile = nullptr; // window-blocked CSC: nwin+1 big-tile ranges of the windows
+    int nbig = 0;          // stream plan, LDS-staged variant, and window-blocked CSC: number of big tiles
     int *d_big = nullptr;  // nbig x int4 {s0, s1, k0, k1} (<= 8189 nnz, <= 1024 segments each)
 };
 
@@ -255,11 +254,11 @@ struct lsq_mat {
     double *d_colsum_base = nullptr;           // fused mode: colsumabs2(V)
     unsigned long long base_version = 0;       // bumps whenever V changes
     unsigned long long colsum_base_version = ~0ull;
-    // Row-window-blocked CSC for J'*y when the gathered m-vector outgrows an XCD's L2 (4 MiB):
-    // rows are cut into `nwin` windows; segment (w, j) holds column j's entries with rows in
-    // window w, so all gathers of a window hit a <= 1 MiB slice of y that stays L2-resident on
-    // the XCD the window is scheduled on.  Per-window column sums land in d_bpart (nwin x n)
-    // and are combined in index order by k_combine.
+    // Row-window-blocked CSC for J'*y when the gathered m-vector is large and the sliced columns are not built
+    // (nwin > 1, else unused): rows are cut into `nwin` windows of <= 4096 rows; segment (w, j) holds column j's
+    // entries with rows in window w, so a workgroup gathers from a copy of y[window] in LDS (k_bcsc_lds; the
+    // segments carry no launch plan of their own).  Per-window column sums land in d_bpart (nwin x n, or
+    // nwin x 2n with the squares) and are combined in index order by k_combine.
     LsqSegs bcsc;
     int nwin = 0;
     int *d_bmap = nullptr;  // bcsc position -> csc position

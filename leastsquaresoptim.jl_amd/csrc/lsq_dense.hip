@@ -12,7 +12,7 @@
 #include "lsq_solver.h"
 #include "lsq_spmv.h"
 
-// allow_tiles: the one-launch factorisation (k_chol_tiles) may be used; the caller then handles info == -1 (a bounded wait gave up)
+// allow_tiles: the one-launch factorisation (k_chol_chain) may be used; the caller then handles info == -1 (a bounded wait gave up)
 int lsq_cholesky_blocked(lsq_solver *s, lsq_mat *J, const double *d_damp, double *d_x, double *d_dmax, bool allow_tiles = false,
                          const double *d_y = nullptr);
 int lsq_cholesky_blocked_solve(lsq_solver *s, int n, double *d_x);
@@ -391,7 +391,7 @@ int lsq_cholesky_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const doubl
         LSQ_TRY(factor_and_solve(true));
         s->last_chol_path = s->last_chol_tiles ? 4 : 2;
         int info = st4[0], perr = st4[1];
-        if (info == -1) {                         // k_chol_tiles gave up on a wait: panel launches for a while, and redo
+        if (info == -1) {                         // k_chol_chain gave up on a wait: panel launches for a while, and redo
             s->fb_tiles.gave_up(c, LSQ_FB_CHOL_TILES);
             s->last_chol_path = 2;
             LSQ_TRY(factor_and_solve(false));

@@ -225,20 +225,17 @@ k_chol_panel_mfma(double *__restrict__ C, int n, int j0, int *__restrict__ info,
     }
 }
 
-// ---- the whole blocked factorisation as ONE launch for n <= 64 * 22 (at most one 64 x 64 upper tile per CU) ------------
-// Workgroup (i, j), i <= j, owns tile (i, j) of J'J + D and keeps it in LDS from the first to the last instruction:
-//     for k < i:   wait for U(k, i) and U(k, j);   tile -= U(k, i)' U(k, j)                 (right-looking, MFMA)
-//     i == j:      U(i, i) = chol(tile), inv(U(i, i)) -> Xd[i]; publish
-//     i <  j:      wait for (i, i);   U(i, j) = inv(U(i, i))' tile; publish
+// ---- the whole blocked factorisation as ONE launch for n <= 64 * 22 (at most one 64 x 64 upper tile per CU): k_chol_chain ----
+// The helpers below are what its workgroups exchange tiles with.  Workgroup (i, j), i <= j, owns tile (i, j) of J'J + D and
+// keeps it in LDS from the first to the last instruction; the right-looking updates tile -= U(k, i)' U(k, j) run on the MFMA
+// unit as soon as the tiles of row k are there.
 // "publish" = the tile goes to global memory with agent-scope stores, every wave drains them, then one epoch-tagged flag
-// is released (flags are never reset: the epoch changes with every factorisation).  Workgroup (i, j) only ever waits for
-// tiles of rows < i or for (i, i), so the waits cannot form a cycle as long as every workgroup is resident -- one per CU
-// here (the caller checks tiles <= CUs).  Waits are bounded (CHT_SPIN_LIMIT polls): a workgroup that gives up writes
-// info = -1, releases its own flag so that nobody waits for IT, and the host repeats the factorisation with the
-// launch-per-panel path.  Against that path (8 x (24 us panel + 10 us update + launch gaps) at n = 512) the chain per
-// 64 columns is: factor + inverse 14 us, one flag, 5 us row-panel tile, one flag, 4 us update of the next diagonal tile.
-constexpr size_t CHT_LDS = (size_t)(3 * S64_MAT + S64_TMP) * sizeof(double);
-constexpr size_t CHC_LDS = (size_t)(4 * S64_MAT + S64_TMP) * sizeof(double);   // k_chol_chain: + the next diagonal tile
+// is released (flags are never reset: the epoch changes with every factorisation).  A workgroup only ever waits for tiles
+// of earlier rows or for its own row's diagonal tile, so the waits cannot form a cycle as long as every workgroup is
+// resident -- one per CU here (the caller checks tiles + 1 <= CUs).  Waits are bounded (CHT_SPIN_LIMIT polls): a workgroup
+// that gives up writes info = -1, releases its own flag so that nobody waits for IT, and the host repeats the factorisation
+// with the launch-per-panel path (8 x (24 us panel + 10 us update + launch gaps) at n = 512).
+constexpr size_t CHC_LDS = (size_t)(4 * S64_MAT + S64_TMP) * sizeof(double);   // three tiles, scratch, the next diagonal tile
 constexpr int CHT_SPIN_LIMIT = 1 << 22;
 __device__ __forceinline__ bool cht_wait(const unsigned *flag, unsigned epoch, int *info, int spin_limit,
                                          const unsigned *flag2 = nullptr) {   // flag2: a second flag to wait for (same bound)
@@ -325,85 +322,11 @@ __device__ __forceinline__ void cht_publish(double *C, int n, int ti, int tj, co
     if (tid == 0) __hip_atomic_store(flag, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__global__ void __launch_bounds__(256)
-k_chol_tiles(double *C, int n, int nt, int *info, double *Xd, unsigned *flags,   // (no __restrict__: workgroups exchange tiles through C and Xd)
-             unsigned epoch, unsigned wait_epoch, int spin_limit) {   // (wait_epoch != epoch: the tests' fault injector)
-    extern __shared__ __attribute__((aligned(16))) double sm[];
-    double *M0 = sm, *M1 = sm + S64_MAT, *M2 = sm + 2 * S64_MAT, *T = sm + 3 * S64_MAT;
-    __shared__ int s_fail;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    int t = blockIdx.x, ti = 0;
-    while (t >= nt - ti) { t -= nt - ti; ++ti; }
-    const int tj = ti + t;
-    unsigned *myflag = flags + ti * nt + tj;
-    cht_load<false>(M0, C, n, ti, tj, tid);
-    __syncthreads();
-    bool ok = true;
-    for (int k = 0; k < ti && ok; ++k) {
-        ok = cht_wait(flags + k * nt + ti, wait_epoch, info, spin_limit);
-        if (ok && tj != ti) ok = cht_wait(flags + k * nt + tj, wait_epoch, info, spin_limit);
-        if (!ok) break;
-        cht_load<true>(M1, C, n, k, ti, tid);               // U(k, i): rows = the k index
-        if (tj != ti) cht_load<true>(M2, C, n, k, tj, tid);
-        __syncthreads();
-        const double *B = tj != ti ? M2 : M1;
-        for (int q = wv; q < 16; q += 4) {                  // tile -= U(k, i)' U(k, j)
-            const int a = q >> 2, b = q & 3;
-            if (ti == tj && a > b) continue;                // (only the upper triangle of a diagonal tile is read later)
-            s64_v4d acc = {0.0, 0.0, 0.0, 0.0};
-            s64_tile_mma<true, false>(acc, M1, 0, 16 * a, B, 0, 16 * b, 4, lane);
-            s64_tile_store<true>(M0, 16 * a, 16 * b, acc, -1.0, lane);
-        }
-        __syncthreads();
-    }
-    if (!ok) {   // a tile this one needs never arrived: let the tiles waiting for THIS one go (the host sees info = -1)
-        if (tid == 0) __hip_atomic_store(myflag, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    if (ti == tj) {
-        const int bad = s64_chol(M0, M1, &s_fail, tid);
-        if (bad) {
-            if (tid == 0) {
-                atomicCAS(info, 0, 64 * ti + bad);          // PosDefException position (1-based); the first failure wins
-                __hip_atomic_store(myflag, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            return;
-        }
-        s64_chol_inverse(M0, M1, T, tid);                   // M1 = inv(U(i, i))
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {                      // the pipelined triangular solves and the row panel read Xd[i]
-            const int e = tid + 256 * q, r = e & 63, c = e >> 6;
-            const bool in = 64 * ti + r < n && 64 * ti + c < n;
-            __hip_atomic_store(Xd + (size_t)ti * 4096 + (size_t)c * 64 + r, in ? M1[r * S64_LS + c] : 0.0, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-        }
-        cht_publish(C, n, ti, tj, M0, true, myflag, epoch, tid);
-    } else {
-        if (!cht_wait(flags + ti * nt + ti, wait_epoch, info, spin_limit)) {
-            if (tid == 0) __hip_atomic_store(myflag, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            return;
-        }
-        {   // inv(U(i, i)) (column-major 64 x 64 in Xd) -> M1 [r][c]
-            double g[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q)
-                g[q] = __hip_atomic_load(Xd + (size_t)ti * 4096 + tid + 256 * q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int e = tid + 256 * q, r = e & 63, c = e >> 6;
-                M1[r * S64_LS + c] = g[q];
-            }
-        }
-        __syncthreads();
-        s64_gemm<true, false, S64_LF>(M2, M1, M0, 1.0, tid);   // U(i, j) = inv(U(i, i))' tile
-        cht_publish(C, n, ti, tj, M2, false, myflag, epoch, tid);
-    }
-}
-
-// ---- the same factorisation with the DIAGONAL CHAIN inside one workgroup ----------------------------------------------
-// In k_chol_tiles every 64 columns of the critical path cross workgroups twice: (i, i) -> flag -> (i, i+1) -> flag ->
-// (i+1, i+1), each hop a drain of the stores, a release, a poll and a reload of a 32 KB tile (~26 us per 64 columns for
-// ~14 us of arithmetic).  Here workgroup 0 (the chain) keeps the whole path local:
+// ---- the factorisation with the DIAGONAL CHAIN inside one workgroup -------------------------------------------------------
+// With one workgroup per tile and nothing else, every 64 columns of the critical path cross workgroups twice: (i, i) ->
+// flag -> (i, i+1) -> flag -> (i+1, i+1), each hop a drain of the stores, a release, a poll and a reload of a 32 KB tile
+// (~26 us per 64 columns for ~14 us of arithmetic; measured in round 2).  Here workgroup 0 (the chain) keeps the whole path
+// local:
 //     chain, step i:   M0 = T2'(i) - U(i-1, i)' U(i-1, i)   (T2' = the diagonal tile with the terms k <= i-2 applied, published
 //                                                             by the helper of (i, i); U(i-1, i) is still in this LDS)
 //                      U(i, i) = chol(M0);  publish it with the four inv(U_kk)' blocks (Wd)              -> flag D(i)
@@ -416,8 +339,8 @@ k_chol_tiles(double *C, int n, int nt, int *info, double *Xd, unsigned *flags,  
 //                      on anybody's path)
 // The helpers' inputs are ready a whole chain step early (the chain is the slowest producer), so the chain's own waits are
 // normally satisfied at once.  Deadlock: the chain waits for helpers of rows <= i, they wait for tiles of rows < i and for
-// D(<= i); no cycle, all workgroups resident (tiles + 1 <= CUs).  Giving up / a non-positive pivot: as in k_chol_tiles,
-// plus the chain releases every flag it owns.
+// D(<= i); no cycle, all workgroups resident (tiles + 1 <= CUs).  Giving up: as above, and the chain releases every flag it
+// owns.  A non-positive pivot: info = 1 + its index (the first failure wins), flags released likewise.
 // X (64 x 64, LDS) <- inv(U)' X for an upper triangular U whose inv(U_kk)' blocks are the diagonal blocks of W: forward
 // substitution over the four block rows; wavefront = 16 columns, which it carries through all four stages in registers --
 // the accumulator layout of v_mfma_f64_16x16x4 (lane (j, q) holds rows q + 4 r) IS the B-operand layout of the next product
@@ -525,7 +448,9 @@ __device__ __forceinline__ void chc_load_w(double *W, const double *Wd, int i, i
 
 __global__ void __launch_bounds__(256)
 k_chol_chain(double *C, int n, int nt, int *info, double *Xd, double *Wd, unsigned *flags, unsigned *pflags,
-             unsigned epoch, unsigned wait_epoch, int spin_limit, long long *trace,   // trace: LSQ_CHOL_TRACE (10 ns ticks)
+             unsigned epoch, unsigned wait_epoch, int spin_limit,   // (wait_epoch != epoch: the tests' fault injector)
+             long long *trace,   // phase stamps (10 ns ticks) for a debugging build; the library passes null.  Kept: the kernel
+                                 // compiled without the stamp sites measured up to 1.4 % slower at 4096 x 512 (LABNOTES, 2026-10-19)
              const double *bvec, double *zvec, unsigned long long *zslot, unsigned zep, int *zerr) {   // bvec: + U'z = b (see below)
 #define CHC_STAMP(p) do { if (trace && tid == 0) trace[i * 16 + (p)] = wall_clock64(); } while (0)
     extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -951,12 +876,12 @@ int lsq_cholesky_blocked(lsq_solver *s, lsq_mat *J, const double *d_damp, double
         LSQ_LAUNCH(k_syrk_reduce, dim3(ntiles * 16), dim3(256), 0, c->stream, s->d_T, n, kslices, d_damp, s->d_chol, s->d_info);
     }
     if (d_dmax) LSQ_LAUNCH(k_diag_max, dim3(1), dim3(256), 0, c->stream, s->d_chol, n, d_dmax);
-    // one launch for the whole factorisation when every 64 x 64 upper tile gets a CU of its own (k_chol_tiles)
-    if (allow_tiles && !s->fb_tiles.off() && ntiles <= c->num_cus && n >= 2 * NB && !getenv("LSQ_CHOL_PANELS")) {
+    // one launch for the whole factorisation when the chain and every 64 x 64 upper tile get a CU of their own (k_chol_chain)
+    if (allow_tiles && !s->fb_tiles.off() && ntiles + 1 <= c->num_cus && n >= 2 * NB && !getenv("LSQ_CHOL_PANELS")) {
         double *Xt = lsq_tri_chol_diagbuf(s, n);
         if (Xt) {
             // flags: [0, 1024) 'tile final' (D on the diagonal), [1024, 2048) 'partial tile for the chain'; then the
-            // 16 x 16 inverse blocks of the diagonal tiles (k_chol_chain)
+            // 16 x 16 inverse blocks of the diagonal tiles
             constexpr size_t FLAG_BYTES = 2 * 32 * 32 * sizeof(unsigned);
             if (!s->d_chol_flags) {
                 LSQ_HIP(hipMalloc(&s->d_chol_flags, FLAG_BYTES + 32 * 1024 * sizeof(double)));
@@ -965,45 +890,17 @@ int lsq_cholesky_blocked(lsq_solver *s, lsq_mat *J, const double *d_damp, double
             if (++s->chol_epoch == 0) ++s->chol_epoch;
             const bool inject = getenv("LSQ_TEST_EXCHANGE_TIMEOUT") != nullptr;   // the waits never see their flag
             const unsigned wait_epoch = inject ? s->chol_epoch ^ 0x40000000u : s->chol_epoch;
-            static const bool v1 = getenv("LSQ_CHOL_TILES_V1") != nullptr;      // (A/B: the chain across workgroups)
-            if (!v1 && ntiles + 1 <= c->num_cus) {
-                LSQ_TRY(lsq_set_lds(c, (const void *)k_chol_chain, CHC_LDS));
-                static const bool tracing = getenv("LSQ_CHOL_TRACE") != nullptr;   // (debug: the chain's phase stamps)
-                static long long *d_trace = nullptr;
-                if (tracing && !d_trace) { LSQ_HIP(hipMalloc(&d_trace, 64 * 16 * sizeof(long long))); }
-                // with a right-hand side at hand the forward half of the solve rides along: nt more workgroups
-                double *zv = nullptr;
-                unsigned long long *zslot = nullptr, zep = 0;
-                int *zerr = nullptr;
-                static const bool nofuse = getenv("LSQ_CHOL_NO_FUSED_FSOLVE") != nullptr;     // (A/B)
-                const bool fuse = d_x && !nofuse && ntiles + 1 + nt <= c->num_cus &&
-                                  lsq_tri_chol_fwd_operands(s, n, &zv, &zslot, &zep, &zerr) == LSQ_OK;
-                LSQ_LAUNCH(k_chol_chain, dim3(ntiles + 1 + (fuse ? nt : 0)), dim3(256), CHC_LDS, c->stream, s->d_chol, n, nt,
-                                   s->d_info, Xt, (double *)((char *)s->d_chol_flags + FLAG_BYTES), s->d_chol_flags,
-                                   s->d_chol_flags + 1024, s->chol_epoch, wait_epoch, inject ? 64 : CHT_SPIN_LIMIT, d_trace,
-                                   (const double *)(fuse ? d_x : nullptr), zv, zslot, (unsigned)zep, zerr);
-                if (tracing) {
-                    long long h[64 * 16];
-                    LSQ_HIP(hipStreamSynchronize(c->stream));
-                    LSQ_HIP(hipMemcpy(h, d_trace, sizeof h, hipMemcpyDeviceToHost));
-                    static int shown = 0;
-                    if (shown++ % 50 == 10)
-                        for (int i = 0; i < nt; ++i) {
-                            fprintf(stderr, "chain step %2d: chol %.2f", i, (h[i * 16 + 1] - h[i * 16]) * 0.01);
-                            if (i + 1 < nt)
-                                fprintf(stderr, " tail+release %.2f trsm %.2f store %.2f syrk %.2f   total %.2f us", (h[i * 16 + 3] - h[i * 16 + 1]) * 0.01,
-                                        (h[i * 16 + 4] - h[i * 16 + 3]) * 0.01, (h[i * 16 + 6] - h[i * 16 + 4]) * 0.01,
-                                        (h[i * 16 + 5] - h[i * 16 + 6]) * 0.01, (h[(i + 1) * 16] - h[i * 16]) * 0.01);
-                            fprintf(stderr, "\n    chol:");
-                            for (int p = 0; p < 12; ++p) fprintf(stderr, " %.2f", (h[512 + i * 16 + p] - (p ? h[512 + i * 16 + p - 1] : h[i * 16])) * 0.01);
-                            fprintf(stderr, "\n");
-                        }
-                }
-            } else {
-                LSQ_TRY(lsq_set_lds(c, (const void *)k_chol_tiles, CHT_LDS));
-                LSQ_LAUNCH(k_chol_tiles, dim3(ntiles), dim3(256), CHT_LDS, c->stream, s->d_chol, n, nt, s->d_info, Xt,
-                                   s->d_chol_flags, s->chol_epoch, wait_epoch, inject ? 64 : CHT_SPIN_LIMIT);
-            }
+            LSQ_TRY(lsq_set_lds(c, (const void *)k_chol_chain, CHC_LDS));
+            // with a right-hand side at hand the forward half of the solve rides along: nt more workgroups
+            double *zv = nullptr;
+            unsigned long long *zslot = nullptr, zep = 0;
+            int *zerr = nullptr;
+            const bool fuse = d_x && ntiles + 1 + nt <= c->num_cus &&
+                              lsq_tri_chol_fwd_operands(s, n, &zv, &zslot, &zep, &zerr) == LSQ_OK;
+            LSQ_LAUNCH(k_chol_chain, dim3(ntiles + 1 + (fuse ? nt : 0)), dim3(256), CHC_LDS, c->stream, s->d_chol, n, nt,
+                               s->d_info, Xt, (double *)((char *)s->d_chol_flags + FLAG_BYTES), s->d_chol_flags,
+                               s->d_chol_flags + 1024, s->chol_epoch, wait_epoch, inject ? 64 : CHT_SPIN_LIMIT, (long long *)nullptr,
+                               (const double *)(fuse ? d_x : nullptr), zv, zslot, (unsigned)zep, zerr);
             s->chol_have_diaginv = true;
             s->last_chol_tiles = true;
             if (!d_x) { LSQ_HIP(hipGetLastError()); return LSQ_OK; }

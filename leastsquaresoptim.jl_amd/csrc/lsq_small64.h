@@ -119,7 +119,7 @@ __device__ __forceinline__ int s64_chol16(double *__restrict__ M, double *__rest
 // other than (kb, kb) and buffers other than W may be touched).
 struct S64NoIdle { __device__ __forceinline__ void operator()(int, int, int) const {} };
 template <bool ZERO_LOWER = true, class F = S64NoIdle>     // ZERO_LOWER = false: the blocks below the diagonal blocks keep G / garbage
-__device__ __forceinline__ int s64_chol(double *M, double *W, int *fail, int tid, long long *tr = nullptr,   // tr: debug stamps (10 ns)
+__device__ __forceinline__ int s64_chol(double *M, double *W, int *fail, int tid, long long *tr = nullptr,   // tr: debug stamps (10 ns), see k_chol_chain
                                         F idle = F()) {
     const int lane = tid & 63, wv = tid >> 6;
     if (tid == 0) *fail = 0;

@@ -109,9 +109,9 @@ struct lsq_solver {
     int last_chol_path = 0;         // lsq_solver_chol_path
     LsqFallback fb_pipe;            // pipelined triangular solves (else single-workgroup solves)
     bool chol_have_diaginv = false; // the last blocked factorisation left inv(U_kk) in the solve pipeline's buffer
-    unsigned *d_chol_flags = nullptr; // k_chol_tiles: epoch-tagged 'tile published' flags
+    unsigned *d_chol_flags = nullptr; // k_chol_chain: epoch-tagged 'tile published' flags
     unsigned chol_epoch = 0;
-    LsqFallback fb_tiles;           // one-launch factorisation k_chol_tiles (else launch-per-panel)
+    LsqFallback fb_tiles;           // one-launch factorisation k_chol_chain (else launch-per-panel)
     LsqFallback fb_qrx;             // QR: slab exchange of the panel steps + pipelined certified solve (mirrors Qr2Work::no_exchange)
     LsqFallback fb_cholqr{0, 0, 16, false};   // QR: CholeskyQR2 panels (numerical breakdowns; mirrors Qr2Work::no_cholqr)
     bool last_chol_tiles = false;   // the last blocked factorisation was the one-launch one

@@ -9,13 +9,12 @@
 // ---------------------------------------------------------------------------------------------
 // plan construction (host, once per pattern)
 // ---------------------------------------------------------------------------------------------
-static int choose_plan(const char *envname, long long nnz, int nseg, int group_hint = 0) {
+static int choose_plan(const char *envname, long long nnz, int nseg) {
     if (const char *e = getenv(envname)) {
         if (!strcmp(e, "stream")) return LSQ_PLAN_STREAM;
         if (!strcmp(e, "wave")) return LSQ_PLAN_WAVE;
         if (!strcmp(e, "block")) return LSQ_PLAN_BLOCK;
     }
-    if (group_hint > 0 && nseg > 0 && (double)nnz / nseg < 48.0) return LSQ_PLAN_STREAM;
     double avg = nseg > 0 ? (double)nnz / nseg : 0.0;
     if (avg < 48.0) return LSQ_PLAN_STREAM;
     if (avg < 384.0) return LSQ_PLAN_WAVE;
@@ -38,32 +37,10 @@ static void build_tiles(const std::vector<int> &ptr, int nseg, std::vector<int> 
     }
 }
 
-// XCD-aware placement: work item k (a tile, or a block of 4 segments) of window w should run on
-// XCD w % 8, and the dispatcher places block b on XCD b % 8 (observed, used for speed only): deal
-// the work items of each residue class out to the grid positions of that residue.
-static void build_order(const std::vector<int> &item_window, std::vector<int> &order) {
-    const int nw = (int)item_window.size();
-    std::vector<std::vector<int>> byx(8);
-    for (int k = 0; k < nw; ++k) byx[item_window[k] % 8].push_back(k);
-    order.assign(nw, -1);
-    std::vector<size_t> next(8, 0);
-    std::vector<int> leftover;
-    for (int p = 0; p < nw; ++p) {
-        int x = p % 8;
-        if (next[x] < byx[x].size()) order[p] = byx[x][next[x]++];
-    }
-    for (int x = 0; x < 8; ++x)
-        for (size_t k = next[x]; k < byx[x].size(); ++k) leftover.push_back(byx[x][k]);
-    size_t q = 0;
-    for (int p = 0; p < nw; ++p)
-        if (order[p] < 0) order[p] = leftover[q++];
-}
-
-static int upload_segs(lsq_ctx *c, LsqSegs &S, const std::vector<int> &ptr, const std::vector<int> &idx,
-                       const char *envname, int group = 0) {
+// segment boundaries, gather indices and (zeroed) values: what every segment layout has
+static int upload_seg_arrays(LsqSegs &S, const std::vector<int> &ptr, const std::vector<int> &idx) {
     S.nseg = (int)ptr.size() - 1;
     S.nnz = ptr.back();
-    S.plan = choose_plan(envname, S.nnz, S.nseg);
     const size_t pad = 8;
     LSQ_HIP(hipMalloc(&S.d_ptr, (S.nseg + 1) * sizeof(int)));
     LSQ_HIP(hipMalloc(&S.d_idx, (S.nnz + pad) * sizeof(int)));
@@ -72,13 +49,22 @@ static int upload_segs(lsq_ctx *c, LsqSegs &S, const std::vector<int> &ptr, cons
     LSQ_ZERO(S.d_val, 0, (S.nnz + pad) * sizeof(double));
     LSQ_HIP(hipMemcpy(S.d_ptr, ptr.data(), (S.nseg + 1) * sizeof(int), hipMemcpyHostToDevice));
     if (S.nnz) LSQ_HIP(hipMemcpy(S.d_idx, idx.data(), S.nnz * sizeof(int), hipMemcpyHostToDevice));
+    return LSQ_OK;
+}
+
+// the CSC columns / CSR rows with the launch plan of launch_segs
+static int upload_segs(lsq_ctx *c, LsqSegs &S, const std::vector<int> &ptr, const std::vector<int> &idx,
+                       const char *envname) {
+    LSQ_TRY(upload_seg_arrays(S, ptr, idx));
+    S.plan = choose_plan(envname, S.nnz, S.nseg);
+    const size_t pad = 8;
     std::vector<int> tiles;
-    build_tiles(ptr, S.nseg, tiles, group);
+    build_tiles(ptr, S.nseg, tiles);
     S.ntiles = (int)tiles.size() - 1;
     LSQ_HIP(hipMalloc(&S.d_tiles, tiles.size() * sizeof(int)));
     LSQ_HIP(hipMemcpy(S.d_tiles, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice));
     // big tiles for the LDS-staged stream kernel (only worth it on large patterns)
-    if (S.plan == LSQ_PLAN_STREAM && group == 0 && S.nnz >= (1 << 20)) {
+    if (S.plan == LSQ_PLAN_STREAM && S.nnz >= (1 << 20)) {
         // size the big tiles so that every persistent workgroup (one per CU) gets the same count
         std::vector<int> big;
         long long per_round = (long long)LSQ_BIG_NNZ * c->num_cus;
@@ -104,19 +90,6 @@ static int upload_segs(lsq_ctx *c, LsqSegs &S, const std::vector<int> &ptr, cons
             LSQ_HIP(hipMemcpy(S.d_idx16, i16.data(), i16.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
         }
     }
-    if (group > 0 && S.plan != LSQ_PLAN_BLOCK) {
-        std::vector<int> win, order;
-        if (S.plan == LSQ_PLAN_STREAM) {
-            for (int t = 0; t < S.ntiles; ++t) win.push_back(tiles[t] / group);
-        } else {
-            const int per = LSQ_NT / 64;
-            for (int b = 0; b * per < S.nseg; ++b) win.push_back((b * per) / group);
-        }
-        build_order(win, order);
-        LSQ_HIP(hipMalloc(&S.d_order, (order.size() + 1) * sizeof(int)));
-        LSQ_HIP(hipMemcpy(S.d_order, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice));
-    }
-    (void)c;
     return LSQ_OK;
 }
 
@@ -127,7 +100,6 @@ static void free_segs(LsqSegs &S) {
     hipFree(S.d_col16);
     hipFree(S.d_val);
     hipFree(S.d_tiles);
-    hipFree(S.d_order);
     hipFree(S.d_big);
     hipFree(S.d_wtile);
     S = LsqSegs();
@@ -249,6 +221,166 @@ static void free_sell(LsqSell &S) {
     S = LsqSell();
 }
 
+// Sliced rows for J*x: the gather vector in LDS next to the 4096-row output window -- all of it when ncw == 1, else one COLUMN
+// WINDOW of it at a time (k_sell_rows_wide: a row block's workgroup walks the windows in ascending order and keeps the rows'
+// running sums in the output window, so a row is still summed left to right).  rptr / ridx / map: the CSR mirror.
+static int build_sliced_rows(lsq_mat *J, const std::vector<int> &rptr, const std::vector<int> &ridx,
+                             const std::vector<int> &map, int ncw) {
+    lsq_ctx *c = J->ctx;
+    const int m = J->m, n = J->n;
+    int per_cu = (m + c->num_cus - 1) / c->num_cus;
+    int rounds = (per_cu + LSQ_SELL_ROWS_MAX - 1) / LSQ_SELL_ROWS_MAX;
+    int wrows = (m + rounds * c->num_cus - 1) / (rounds * c->num_cus);
+    wrows = std::min(LSQ_SELL_ROWS_MAX, (wrows + 63) & ~63);
+    if (const char *e = getenv("LSQ_SELL_ROWS")) wrows = std::min(LSQ_SELL_ROWS_MAX, std::max(64, atoi(e) & ~63));
+    const int nrb = (m + wrows - 1) / wrows;
+    int st;
+    if (ncw == 1) {
+        st = build_sell(
+            J->srows, nrb, rptr, map,
+            [&](int b, int &first, int &count) { first = b * wrows; count = std::min(wrows, m - first); },
+            [&](int e) { return (unsigned short)ridx[e]; }, [&](int e) { return (unsigned short)ridx[e]; }, false);
+    } else {
+        // sub-rows (window, row): entries of a row keep their column order inside every window
+        const int cwidth = (((n + ncw - 1) / ncw) + 1) & ~1;
+        std::vector<int> wptr((size_t)ncw * m + 1, 0), widx(J->nnz), wmap(J->nnz);
+        for (int i = 0; i < m; ++i)
+            for (int e = rptr[i]; e < rptr[i + 1]; ++e) wptr[(size_t)(ridx[e] / cwidth) * m + i + 1]++;
+        for (size_t s2 = 0; s2 < (size_t)ncw * m; ++s2) wptr[s2 + 1] += wptr[s2];
+        // (a row's entries are sorted by column, so its entries of one window are consecutive: a running offset per
+        //  (row, window) instead of a second ncw * m array of fill positions)
+        for (int i = 0; i < m; ++i) {
+            int w_cur = -1, off = 0;
+            for (int e = rptr[i]; e < rptr[i + 1]; ++e) {
+                const int w = ridx[e] / cwidth;
+                if (w != w_cur) { w_cur = w; off = 0; }
+                const int p = wptr[(size_t)w * m + i] + off++;
+                widx[p] = ridx[e] % cwidth;
+                wmap[p] = map[e];
+            }
+        }
+        st = build_sell(
+            J->srows, nrb * ncw, wptr, wmap,
+            [&](int b, int &first, int &count) {
+                const int rb = b / ncw, cw = b % ncw;
+                first = cw * m + rb * wrows;
+                count = std::min(wrows, m - rb * wrows);
+            },
+            [&](int e) { return (unsigned short)widx[e]; }, [&](int e) { return (unsigned short)widx[e]; }, false, true,
+            /*allow_odd=*/false);
+        J->srows.ncw = ncw;
+        J->srows.cwidth = cwidth;
+        if (st == LSQ_OK) LSQ_HIP(hipMalloc(&J->srows.d_sx, (size_t)n * sizeof(double)));
+    }
+    if (st == LSQ_EDIM) {   // does not fit the slice format: the CSR mirror keeps the product
+        free_sell(J->srows);
+        return LSQ_OK;
+    }
+    if (st != LSQ_OK) return st;
+    J->srows.wrows = wrows;
+    hipFree(J->csr.d_val);   // the sliced layout carries the values; misuse of the mirror must fail loudly
+    J->csr.d_val = nullptr;
+    return LSQ_OK;
+}
+
+// Counting sort of the stored entries by (row / rows_per_win, column): segment w * n + j of `ptr` holds the entries of column j
+// with rows in window w, in their CSC order; idx[p] = the row of sorted entry p, map[p] = its CSC position.
+static void sort_by_row_window(int n, const int *colptr, const int *rowval, int rows_per_win, int nwin, std::vector<int> &ptr,
+                               std::vector<int> &idx, std::vector<int> &map) {
+    const size_t nseg = (size_t)nwin * n;
+    ptr.assign(nseg + 1, 0);
+    idx.resize(colptr[n]);
+    map.resize(colptr[n]);
+    for (int j = 0; j < n; ++j)
+        for (int k = colptr[j]; k < colptr[j + 1]; ++k) ptr[(size_t)(rowval[k] / rows_per_win) * n + j + 1]++;
+    for (size_t s = 0; s < nseg; ++s) ptr[s + 1] += ptr[s];
+    std::vector<int> fill(ptr.begin(), ptr.end() - 1);
+    for (int j = 0; j < n; ++j)
+        for (int k = colptr[j]; k < colptr[j + 1]; ++k) {
+            int p = fill[(size_t)(rowval[k] / rows_per_win) * n + j]++;
+            idx[p] = rowval[k];
+            map[p] = k;
+        }
+}
+
+// Sliced columns for J'*y: ngw gather windows of `grows` rows of y in LDS, ncb blocks of `ccols` output columns each (lsq_sell.h)
+static int build_sliced_cols(lsq_mat *J, const int *colptr, const int *rowval, int ncb, int ccols, int ngw, int grows) {
+    const int n = J->n;
+    std::vector<int> gptr, gidx, gmap;
+    sort_by_row_window(n, colptr, rowval, grows, ngw, gptr, gidx, gmap);
+    std::vector<unsigned short> gcol(J->nnz);
+    for (size_t sg = 0; sg < (size_t)ngw * n; ++sg)
+        for (int e = gptr[sg]; e < gptr[sg + 1]; ++e) gcol[e] = (unsigned short)(sg % n);
+    int st = build_sell(
+        J->scols, ngw * ncb, gptr, gmap,
+        [&](int b, int &first, int &count) {
+            const int gw = b / ncb, cb = b % ncb;
+            first = gw * n + cb * ccols;
+            count = std::max(0, std::min(ccols, n - cb * ccols));
+        },
+        [&](int e) { return (unsigned short)(gidx[e] % grows); }, [&](int e) { return gcol[e]; }, n <= 65535);
+    if (st == LSQ_EDIM) {   // does not fit the slice format: the (windowed) CSC keeps the product
+        free_sell(J->scols);
+        return LSQ_OK;
+    }
+    if (st != LSQ_OK) return st;
+    J->scols.ncb = ncb; J->scols.ccols = ccols; J->scols.ngw = ngw; J->scols.grows = grows;
+    LSQ_HIP(hipMalloc(&J->scols.d_part, (size_t)ngw * n * 2 * sizeof(double)));
+    return LSQ_OK;
+}
+
+// Row-window-blocked CSC for J'*y (k_bcsc_lds): nwin windows of rw <= LSQ_WIN_ROWS_MAX rows of y staged in LDS, the entries of
+// a window cut into big tiles of <= LSQ_BIG_NNZ entries and <= LSQ_WIN_SEGS (window, column) segments that never straddle a
+// window.  Leaves J->nwin at 0 -- the plain CSC column product then runs, which takes segments of any length -- when one
+// (window, column) segment alone is longer than a tile.  A tile holds 8189 entries and a window at most 4096 rows, so that needs
+// more than 8189 stored entries of one column inside one window: impossible for a pattern without repeated row indices in a
+// column (lsq_csc_create does not reject those).
+static int build_windowed_csc(lsq_mat *J, const int *colptr, const int *rowval, int rw, int nwin) {
+    const int n = J->n;
+    const long long nnz = J->nnz;
+    std::vector<int> bptr, bidx, bmap;
+    sort_by_row_window(n, colptr, rowval, rw, nwin, bptr, bidx, bmap);
+    std::vector<int> big;
+    build_tiles(bptr, nwin * n, big, n, LSQ_WIN_SEGS, LSQ_BIG_NNZ);
+    const int nb = (int)big.size() - 1;
+    for (int t = 0; t < nb; ++t)
+        if (bptr[big[t + 1]] - bptr[big[t]] > LSQ_BIG_NNZ) return LSQ_OK;
+    LSQ_TRY(upload_seg_arrays(J->bcsc, bptr, bidx));
+    J->bcsc.rw = rw;
+    J->bcsc.nwin = nwin;
+    std::vector<int> bm((size_t)4 * nb + 4), wt(nwin + 1, 0);
+    for (int t = 0; t < nb; ++t) {
+        bm[4 * t + 0] = big[t];
+        bm[4 * t + 1] = big[t + 1];
+        bm[4 * t + 2] = bptr[big[t]];
+        bm[4 * t + 3] = bptr[big[t + 1]];
+        wt[big[t] / n + 1]++;
+    }
+    for (int w = 0; w < nwin; ++w) wt[w + 1] += wt[w];
+    LSQ_HIP(hipMalloc(&J->bcsc.d_big, bm.size() * sizeof(int)));
+    LSQ_HIP(hipMemcpy(J->bcsc.d_big, bm.data(), bm.size() * sizeof(int), hipMemcpyHostToDevice));
+    LSQ_HIP(hipMalloc(&J->bcsc.d_wtile, wt.size() * sizeof(int)));
+    LSQ_HIP(hipMemcpy(J->bcsc.d_wtile, wt.data(), wt.size() * sizeof(int), hipMemcpyHostToDevice));
+    J->bcsc.nbig = nb;
+    {  // in-window row offsets (< 4096) in 16 bits
+        std::vector<unsigned short> i16(nnz + 8, 0);
+        for (long long k = 0; k < nnz; ++k) i16[k] = (unsigned short)(bidx[k] % rw);
+        LSQ_HIP(hipMalloc(&J->bcsc.d_idx16, i16.size() * sizeof(unsigned short)));
+        LSQ_HIP(hipMemcpy(J->bcsc.d_idx16, i16.data(), i16.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
+        if (n <= 65535) {  // column of each entry, for column-scaling g! kernels
+            for (size_t sg = 0; sg < (size_t)nwin * n; ++sg)
+                for (int k = bptr[sg]; k < bptr[sg + 1]; ++k) i16[k] = (unsigned short)(sg % n);
+            LSQ_HIP(hipMalloc(&J->bcsc.d_col16, i16.size() * sizeof(unsigned short)));
+            LSQ_HIP(hipMemcpy(J->bcsc.d_col16, i16.data(), i16.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
+        }
+    }
+    LSQ_HIP(hipMalloc(&J->d_bmap, (nnz + 8) * sizeof(int)));
+    LSQ_HIP(hipMemcpy(J->d_bmap, bmap.data(), nnz * sizeof(int), hipMemcpyHostToDevice));
+    LSQ_HIP(hipMalloc(&J->d_bpart, (size_t)nwin * n * 2 * sizeof(double)));  // [w][dots | squares]
+    J->nwin = nwin;
+    return LSQ_OK;
+}
+
 static int csc_create_impl(lsq_ctx *c, int m, int n, const int *colptr, const int *rowval, lsq_mat **out);
 extern "C" int lsq_csc_create(lsq_ctx *c, int m, int n, const int *colptr, const int *rowval, lsq_mat **out) {
     LSQ_RANGE("lsq_csc_create");
@@ -307,7 +439,6 @@ static int csc_create_impl(lsq_ctx *c, int m, int n, const int *colptr, const in
     }
     J->csc.nx = m;
     J->csr.nx = n;
-    J->bcsc.nx = m;
     LSQ_TRY(upload_segs(c, J->csc, cptr, cidx, "LSQ_PLAN_CSC"));
     LSQ_TRY(upload_segs(c, J->csr, rptr, ridx, "LSQ_PLAN_CSR"));
     LSQ_HIP(hipMalloc(&J->d_map, (nnz + 4) * sizeof(int)));
@@ -315,9 +446,7 @@ static int csc_create_impl(lsq_ctx *c, int m, int n, const int *colptr, const in
     LSQ_HIP(hipMalloc(&J->d_colsum, (n > 0 ? n : 1) * sizeof(double)));
     const bool sell_force = getenv("LSQ_SELL_FORCE") != nullptr;   // tests: sliced layouts on small patterns too
     const bool sell_ok = !getenv("LSQ_NO_SELL") && (sell_force || nnz >= (1 << 20)) && nnz > 0;
-    // sliced rows for J*x: the gather vector in LDS next to the 4096-row output window -- all of it when n <= LSQ_LDS_X_MAX,
-    // else one COLUMN WINDOW of it at a time (k_sell_rows_wide: a row block's workgroup walks the windows in ascending
-    // order and keeps the rows' running sums in the output window, so a row is still summed left to right)
+    // sliced rows for J*x (build_sliced_rows): all of x in LDS when n <= LSQ_LDS_X_MAX, else one column window of it at a time
     int xmax = LSQ_LDS_X_MAX;
     if (const char *e = getenv("LSQ_SELL_XMAX")) xmax = std::min(LSQ_LDS_X_MAX, std::max(64, atoi(e)));   // tests: narrow windows
     else if (n > LSQ_LDS_X_MAX) xmax = LSQ_SELL_WIDE_X_MAX;      // windows may be a little wider than what the one-window kernels hold
@@ -329,64 +458,12 @@ static int csc_create_impl(lsq_ctx *c, int m, int n, const int *colptr, const in
     const bool wide_pays = ncw <= LSQ_SELL_CW_AUTO && nnz / c->num_cus >= (long long)ncw * 6000;
     const bool wide_ok = ncw <= LSQ_SELL_CW_MAX && (long long)ncw * m < 64000000LL && !getenv("LSQ_NO_SELL_WIDE") &&
                          (wide_pays || sell_force || getenv("LSQ_SELL_WIDE"));
-    if (sell_ok && J->csr.plan == LSQ_PLAN_STREAM && n >= 1 && (ncw == 1 || wide_ok)) {
-        int per_cu = (m + c->num_cus - 1) / c->num_cus;
-        int rounds = (per_cu + LSQ_SELL_ROWS_MAX - 1) / LSQ_SELL_ROWS_MAX;
-        int wrows = (m + rounds * c->num_cus - 1) / (rounds * c->num_cus);
-        wrows = std::min(LSQ_SELL_ROWS_MAX, (wrows + 63) & ~63);
-        if (const char *e = getenv("LSQ_SELL_ROWS")) wrows = std::min(LSQ_SELL_ROWS_MAX, std::max(64, atoi(e) & ~63));
-        const int nrb = (m + wrows - 1) / wrows;
-        int st;
-        if (ncw == 1) {
-            st = build_sell(
-                J->srows, nrb, rptr, map,
-                [&](int b, int &first, int &count) { first = b * wrows; count = std::min(wrows, m - first); },
-                [&](int e) { return (unsigned short)ridx[e]; }, [&](int e) { return (unsigned short)ridx[e]; }, false, false,
-                /*allow_odd=*/!getenv("LSQ_SELL_EVEN_ROWS"));
-        } else {
-            // sub-rows (window, row): entries of a row keep their column order inside every window
-            const int cwidth = (((n + ncw - 1) / ncw) + 1) & ~1;
-            std::vector<int> wptr((size_t)ncw * m + 1, 0), widx(nnz), wmap(nnz);
-            for (int i = 0; i < m; ++i)
-                for (int e = rptr[i]; e < rptr[i + 1]; ++e) wptr[(size_t)(ridx[e] / cwidth) * m + i + 1]++;
-            for (size_t s2 = 0; s2 < (size_t)ncw * m; ++s2) wptr[s2 + 1] += wptr[s2];
-            // (a row's entries are sorted by column, so its entries of one window are consecutive: a running offset per
-            //  (row, window) instead of a second ncw * m array of fill positions)
-            for (int i = 0; i < m; ++i) {
-                int w_cur = -1, off = 0;
-                for (int e = rptr[i]; e < rptr[i + 1]; ++e) {
-                    const int w = ridx[e] / cwidth;
-                    if (w != w_cur) { w_cur = w; off = 0; }
-                    const int p = wptr[(size_t)w * m + i] + off++;
-                    widx[p] = ridx[e] % cwidth;
-                    wmap[p] = map[e];
-                }
-            }
-            st = build_sell(
-                J->srows, nrb * ncw, wptr, wmap,
-                [&](int b, int &first, int &count) {
-                    const int rb = b / ncw, cw = b % ncw;
-                    first = cw * m + rb * wrows;
-                    count = std::min(wrows, m - rb * wrows);
-                },
-                [&](int e) { return (unsigned short)widx[e]; }, [&](int e) { return (unsigned short)widx[e]; }, false, true,
-                /*allow_odd=*/false);
-            J->srows.ncw = ncw;
-            J->srows.cwidth = cwidth;
-            if (st == LSQ_OK) LSQ_HIP(hipMalloc(&J->srows.d_sx, (size_t)n * sizeof(double)));
-        }
-        if (st == LSQ_OK) {
-            J->srows.wrows = wrows;
-            hipFree(J->csr.d_val);   // the sliced layout carries the values; misuse of the mirror must fail loudly
-            J->csr.d_val = nullptr;
-        } else if (st != LSQ_EDIM) {
-            return st;
-        } else {
-            free_sell(J->srows);
-        }
-    }
+    if (sell_ok && J->csr.plan == LSQ_PLAN_STREAM && n >= 1 && (ncw == 1 || wide_ok))
+        LSQ_TRY(build_sliced_rows(J, rptr, ridx, map, ncw));
+    // LSQ_WINDOW_ROWS (tests): the LDS-window CSC below on a small matrix, cut into windows of that many rows
+    const char *erows = getenv("LSQ_WINDOW_ROWS");
     // sliced columns for J'*y: gather windows of <= 16384 rows of y in LDS, <= 2560 output columns per block (lsq_sell.h)
-    if (sell_ok && (sell_force || m > 131072) && n >= 1 && !getenv("LSQ_PLAN_BCSC") && !getenv("LSQ_WINDOW_ROWS")) {
+    if (sell_ok && (sell_force || m > 131072) && n >= 1 && !erows) {
         const int ncb = (n + LSQ_SELL_CCOLS_MAX - 1) / LSQ_SELL_CCOLS_MAX;
         const int ccols = (n + ncb - 1) / ncb;
         const int ngw_min = (m + LSQ_SELL_GROWS_MAX - 1) / LSQ_SELL_GROWS_MAX;
@@ -396,123 +473,18 @@ static int csc_create_impl(lsq_ctx *c, int m, int n, const int *colptr, const in
         grows = std::min(LSQ_SELL_GROWS_MAX, (grows + 7) & ~7);
         if (const char *e = getenv("LSQ_SELL_GROWS")) grows = std::min(LSQ_SELL_GROWS_MAX, std::max(64, atoi(e) & ~7));
         ngw = (m + grows - 1) / grows;
-        if ((long long)ngw * n < 200000000LL) {
-            std::vector<int> gptr((size_t)ngw * n + 1, 0), gidx(nnz), gmap(nnz);
-            for (int j = 0; j < n; ++j)
-                for (int k2 = colptr[j]; k2 < colptr[j + 1]; ++k2) gptr[(size_t)(rowval[k2] / grows) * n + j + 1]++;
-            for (size_t s2 = 0; s2 < (size_t)ngw * n; ++s2) gptr[s2 + 1] += gptr[s2];
-            {
-                std::vector<int> fill(gptr.begin(), gptr.end() - 1);
-                for (int j = 0; j < n; ++j)
-                    for (int k2 = colptr[j]; k2 < colptr[j + 1]; ++k2) {
-                        int p = fill[(size_t)(rowval[k2] / grows) * n + j]++;
-                        gidx[p] = rowval[k2];
-                        gmap[p] = k2;
-                    }
-            }
-            std::vector<unsigned short> gcol(nnz);
-            for (size_t sg = 0; sg < (size_t)ngw * n; ++sg)
-                for (int e = gptr[sg]; e < gptr[sg + 1]; ++e) gcol[e] = (unsigned short)(sg % n);
-            int st = build_sell(
-                J->scols, ngw * ncb, gptr, gmap,
-                [&](int b, int &first, int &count) {
-                    const int gw = b / ncb, cb = b % ncb;
-                    first = gw * n + cb * ccols;
-                    count = std::max(0, std::min(ccols, n - cb * ccols));
-                },
-                [&](int e) { return (unsigned short)(gidx[e] % grows); }, [&](int e) { return gcol[e]; }, n <= 65535, false,
-                /*allow_odd=*/!getenv("LSQ_SELL_EVEN_COLS"));
-            if (st == LSQ_OK) {
-                J->scols.ncb = ncb; J->scols.ccols = ccols; J->scols.ngw = ngw; J->scols.grows = grows;
-                LSQ_HIP(hipMalloc(&J->scols.d_part, (size_t)ngw * n * 2 * sizeof(double)));
-            } else if (st != LSQ_EDIM) {
-                return st;
-            } else {
-                free_sell(J->scols);
-            }
-        }
+        if ((long long)ngw * n < 200000000LL) LSQ_TRY(build_sliced_cols(J, colptr, rowval, ncb, ccols, ngw, grows));
     }
-    // window-blocked CSC when the gathered m-vector is larger than ~1 MiB.  Default plan: windows
-    // of <= 4096 rows staged in LDS (k_bcsc_lds), sized so that every CU gets a whole number of
-    // windows; LSQ_WINDOW_ROWS / LSQ_PLAN_BCSC select the L2-resident variants instead.
-    {
-        const char *eplan = getenv("LSQ_PLAN_BCSC");
-        const char *erows = getenv("LSQ_WINDOW_ROWS");
-        bool ldswin = !eplan || !strcmp(eplan, "ldswin");
-        int rows_per_win = 131072;
-        if (erows) rows_per_win = std::max(64, atoi(erows));
-        const bool wanted = !J->scols.active && (erows ? m > rows_per_win : m > 131072);
-        if (ldswin && wanted) {
-            int per_cu = (m + c->num_cus - 1) / c->num_cus;
-            int rounds = (per_cu + LSQ_WIN_ROWS_MAX - 1) / LSQ_WIN_ROWS_MAX;
-            rows_per_win = (m + rounds * c->num_cus - 1) / (rounds * c->num_cus);
-            rows_per_win = std::min(LSQ_WIN_ROWS_MAX, (rows_per_win + 7) & ~7);
-            if (erows) rows_per_win = std::min(LSQ_WIN_ROWS_MAX, std::max(64, atoi(erows)));
-        }
-        int nwin = (m + rows_per_win - 1) / rows_per_win;
-        if (wanted && nwin > 1 && nnz > 0 && (long long)nwin * n < 200000000LL) {
-            const int rw = ldswin ? rows_per_win : (m + nwin - 1) / nwin;
-            nwin = (m + rw - 1) / rw;
-            std::vector<int> bptr((size_t)nwin * n + 1, 0), bidx(nnz), bmap(nnz);
-            for (int j = 0; j < n; ++j)
-                for (int k = colptr[j]; k < colptr[j + 1]; ++k) bptr[(size_t)(rowval[k] / rw) * n + j + 1]++;
-            for (size_t s2 = 0; s2 < (size_t)nwin * n; ++s2) bptr[s2 + 1] += bptr[s2];
-            std::vector<int> fill(bptr.begin(), bptr.end() - 1);
-            for (int j = 0; j < n; ++j)
-                for (int k = colptr[j]; k < colptr[j + 1]; ++k) {
-                    int p = fill[(size_t)(rowval[k] / rw) * n + j]++;
-                    bidx[p] = rowval[k];
-                    bmap[p] = k;
-                }
-            LSQ_TRY(upload_segs(c, J->bcsc, bptr, bidx, "LSQ_PLAN_BCSC", n));
-            J->bcsc.rw = rw;
-            J->bcsc.nwin = nwin;
-            if (ldswin) {
-                // big tiles that never straddle a window; segments longer than a tile disable the plan
-                std::vector<int> big;
-                build_tiles(bptr, J->bcsc.nseg, big, n, LSQ_WIN_SEGS, LSQ_BIG_NNZ);
-                int nb = (int)big.size() - 1;
-                bool ok = true;
-                for (int t = 0; t < nb; ++t)
-                    if (bptr[big[t + 1]] - bptr[big[t]] > LSQ_BIG_NNZ) ok = false;
-                if (ok) {
-                    std::vector<int> bm((size_t)4 * nb + 4), wt(nwin + 1, 0);
-                    for (int t = 0; t < nb; ++t) {
-                        bm[4 * t + 0] = big[t];
-                        bm[4 * t + 1] = big[t + 1];
-                        bm[4 * t + 2] = bptr[big[t]];
-                        bm[4 * t + 3] = bptr[big[t + 1]];
-                        wt[big[t] / n + 1]++;
-                    }
-                    for (int w = 0; w < nwin; ++w) wt[w + 1] += wt[w];
-                    hipFree(J->bcsc.d_big);
-                    LSQ_HIP(hipMalloc(&J->bcsc.d_big, bm.size() * sizeof(int)));
-                    LSQ_HIP(hipMemcpy(J->bcsc.d_big, bm.data(), bm.size() * sizeof(int), hipMemcpyHostToDevice));
-                    LSQ_HIP(hipMalloc(&J->bcsc.d_wtile, wt.size() * sizeof(int)));
-                    LSQ_HIP(hipMemcpy(J->bcsc.d_wtile, wt.data(), wt.size() * sizeof(int), hipMemcpyHostToDevice));
-                    J->bcsc.nbig = nb;
-                    J->bcsc.plan = LSQ_PLAN_LDSWIN;
-                    {  // in-window row offsets (< 4096) in 16 bits
-                        std::vector<unsigned short> i16(nnz + 8, 0);
-                        for (long long k = 0; k < nnz; ++k) i16[k] = (unsigned short)(bidx[k] % rw);
-                        LSQ_HIP(hipMalloc(&J->bcsc.d_idx16, i16.size() * sizeof(unsigned short)));
-                        LSQ_HIP(hipMemcpy(J->bcsc.d_idx16, i16.data(), i16.size() * sizeof(unsigned short),
-                                          hipMemcpyHostToDevice));
-                        if (n <= 65535) {  // column of each entry, for column-scaling g! kernels
-                            for (size_t sg = 0; sg < (size_t)nwin * n; ++sg)
-                                for (int k = bptr[sg]; k < bptr[sg + 1]; ++k) i16[k] = (unsigned short)(sg % n);
-                            LSQ_HIP(hipMalloc(&J->bcsc.d_col16, i16.size() * sizeof(unsigned short)));
-                            LSQ_HIP(hipMemcpy(J->bcsc.d_col16, i16.data(), i16.size() * sizeof(unsigned short),
-                                              hipMemcpyHostToDevice));
-                        }
-                    }
-                }
-            }
-            LSQ_HIP(hipMalloc(&J->d_bmap, (nnz + 8) * sizeof(int)));
-            LSQ_HIP(hipMemcpy(J->d_bmap, bmap.data(), nnz * sizeof(int), hipMemcpyHostToDevice));
-            LSQ_HIP(hipMalloc(&J->d_bpart, (size_t)nwin * n * 2 * sizeof(double)));  // [w][dots | squares]
-            J->nwin = nwin;
-        }
+    // window-blocked CSC when the gathered m-vector is larger than ~1 MiB and the sliced columns are not built: windows of
+    // <= 4096 rows staged in LDS (k_bcsc_lds), sized so that every CU gets a whole number of windows
+    if (!J->scols.active && (erows ? m > std::max(64, atoi(erows)) : m > 131072)) {
+        int per_cu = (m + c->num_cus - 1) / c->num_cus;
+        int rounds = (per_cu + LSQ_WIN_ROWS_MAX - 1) / LSQ_WIN_ROWS_MAX;
+        int rw = (m + rounds * c->num_cus - 1) / (rounds * c->num_cus);
+        rw = std::min(LSQ_WIN_ROWS_MAX, (rw + 7) & ~7);
+        if (erows) rw = std::min(LSQ_WIN_ROWS_MAX, std::max(64, atoi(erows)));
+        const int nwin = (m + rw - 1) / rw;
+        if (nwin > 1 && nnz > 0 && (long long)nwin * n < 200000000LL) LSQ_TRY(build_windowed_csc(J, colptr, rowval, rw, nwin));
     }
     J->csr_fresh = true;  // all zeros
     *out = J;
@@ -903,7 +875,7 @@ struct EpiGradSq {
 bool lsq_can_fuse_grad_colsum(const lsq_mat *J) {
     // 160 KiB of dynamic LDS: yl + products + squares
     if (J->kind == LSQ_MAT_CSC && J->scols.active && !lsq_small_mat(J)) return true;
-    if (J->kind != LSQ_MAT_CSC || J->nwin <= 1 || J->bcsc.plan != LSQ_PLAN_LDSWIN || lsq_small_mat(J)) return false;
+    if (J->kind != LSQ_MAT_CSC || J->nwin <= 1 || lsq_small_mat(J)) return false;
     const size_t lds = (size_t)(LSQ_WIN_ROWS_MAX + 2 * LSQ_BIG_WINDOW) * sizeof(double);
     return lsq_set_lds(J->ctx, (const void *)k_bcsc_lds<true, true>, lds) == LSQ_OK &&
            lsq_set_lds(J->ctx, (const void *)k_bcsc_lds<false, true>, lds) == LSQ_OK;

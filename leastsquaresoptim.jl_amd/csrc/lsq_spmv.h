@@ -33,7 +33,6 @@ struct SegsDev {
     const double *val;
     const int *tiles;
     const unsigned short *idx16;
-    const int *order;  // optional work-item permutation
     int nseg;
     int ntiles;
     int nnz;
@@ -157,8 +156,7 @@ __global__ void __launch_bounds__(LSQ_NT) k_seg_stream(SegsDev S, const double *
             epi.extra(bb - S.ntiles, racc);
             continue;
         }
-        const int b = S.order ? S.order[bb] : bb;
-        const int s0 = S.tiles[b], s1 = S.tiles[b + 1];
+        const int s0 = S.tiles[bb], s1 = S.tiles[bb + 1];
         const int k0 = S.ptr[s0], k1 = S.ptr[s1];
         if (k1 - k0 <= LSQ_TILE_NNZ) {
             const int ka = k0 & ~3;  // 32-byte aligned for val, 16-byte for idx
@@ -544,8 +542,7 @@ __global__ void __launch_bounds__(LSQ_NT) k_seg_wave(SegsDev S, const double *__
             epi.extra(bb - nsegblocks, racc);
             continue;
         }
-        const int b = S.order ? S.order[bb] : bb;
-        const int s = b * (LSQ_NT / 64) + w;
+        const int s = bb * (LSQ_NT / 64) + w;
         if (s < S.nseg) {
             const int k0 = S.ptr[s], k1 = S.ptr[s + 1];
             double sum = wave_sum(seg_partial<SQ, 64>(S, x, k0, k1, lane));
@@ -575,7 +572,7 @@ __global__ void __launch_bounds__(LSQ_NT) k_seg_block(SegsDev S, const double *_
 }
 
 static inline SegsDev segs_dev(const LsqSegs &s) {
-    return SegsDev{s.d_ptr, s.d_idx, s.d_val, s.d_tiles, s.d_idx16, s.d_order, s.nseg, s.ntiles, (int)s.nnz};
+    return SegsDev{s.d_ptr, s.d_idx, s.d_val, s.d_tiles, s.d_idx16, s.nseg, s.ntiles, (int)s.nnz};
 }
 
 // Launch the plan chosen for `segs`.  Work items = segment blocks + epi.extra_blocks; the grid is
@@ -761,19 +758,6 @@ __global__ void __launch_bounds__(LSQ_NT) k_dense_t_win(const double *__restrict
 }
 // window count for a dense m x n matrix (0: one block per column is fine)
 
-// Per-window column sums -> d_bpart[w*n + j] (first pass of the window-blocked J'*y)
-struct EpiPart {
-    static constexpr bool REDUCE = false;
-    const int *done;
-    int extra_blocks;
-    double *part;
-    double *partials;
-    unsigned *counter;
-    __device__ void seg(int s, double dot, double &) const { part[s] = dot; }
-    __device__ void extra(int, double &) const {}
-    __device__ void finalize(double) const {}
-};
-
 // second pass: column j = sum over windows, then the caller's epilogue.  A block owns 32 columns;
 // 8 thread groups each add every 8th window in index order (8 loads in flight per thread), and
 // the 8 group sums are added in index order -- a fixed association, hence deterministic.
@@ -957,25 +941,20 @@ static inline int launch_product(lsq_mat *J, int trans, const double *x, const E
         }
         if (J->nwin > 1) {
             LSQ_TRY(lsq_ensure_csr(J));
-            if (J->bcsc.plan == LSQ_PLAN_LDSWIN) {
-                const size_t lds = (size_t)(LSQ_WIN_ROWS_MAX + LSQ_BIG_WINDOW) * sizeof(double);
-                const bool i16 = J->bcsc.d_idx16 != nullptr;
-                auto kern = i16 ? k_bcsc_lds<true, false> : k_bcsc_lds<false, false>;
-                LSQ_TRY(lsq_set_lds(c, (const void *)kern, lds));
-                int g2 = std::max(1, std::min(J->bcsc.nwin, c->num_cus));
-                hipEvent_t e0, e1;
-                if (lsq_prof_take(c, &e0, &e1))
-                    LSQ_LAUNCH_TIMED(kern, dim3(g2), dim3(LSQ_BIG_NT), lds, c->stream, e0, e1, 0, segs_dev(J->bcsc),
-                                          (const int4 *)J->bcsc.d_big, J->bcsc.d_wtile, J->bcsc.nwin, J->bcsc.rw, J->m,
-                                          J->n, x, J->d_bpart, epi.done);
-                else
-                    LSQ_LAUNCH(kern, dim3(g2), dim3(LSQ_BIG_NT), lds, c->stream, segs_dev(J->bcsc),
-                                       (const int4 *)J->bcsc.d_big, J->bcsc.d_wtile, J->bcsc.nwin, J->bcsc.rw, J->m,
-                                       J->n, x, J->d_bpart, epi.done);
-            } else {
-                EpiPart ep{epi.done, 0, J->d_bpart, nullptr, nullptr};
-                LSQ_TRY(launch_segs<false>(c, J->bcsc, x, ep));
-            }
+            const size_t lds = (size_t)(LSQ_WIN_ROWS_MAX + LSQ_BIG_WINDOW) * sizeof(double);
+            const bool i16 = J->bcsc.d_idx16 != nullptr;
+            auto kern = i16 ? k_bcsc_lds<true, false> : k_bcsc_lds<false, false>;
+            LSQ_TRY(lsq_set_lds(c, (const void *)kern, lds));
+            int g2 = std::max(1, std::min(J->bcsc.nwin, c->num_cus));
+            hipEvent_t e0, e1;
+            if (lsq_prof_take(c, &e0, &e1))
+                LSQ_LAUNCH_TIMED(kern, dim3(g2), dim3(LSQ_BIG_NT), lds, c->stream, e0, e1, 0, segs_dev(J->bcsc),
+                                      (const int4 *)J->bcsc.d_big, J->bcsc.d_wtile, J->bcsc.nwin, J->bcsc.rw, J->m,
+                                      J->n, x, J->d_bpart, epi.done);
+            else
+                LSQ_LAUNCH(kern, dim3(g2), dim3(LSQ_BIG_NT), lds, c->stream, segs_dev(J->bcsc),
+                                   (const int4 *)J->bcsc.d_big, J->bcsc.d_wtile, J->bcsc.nwin, J->bcsc.rw, J->m,
+                                   J->n, x, J->d_bpart, epi.done);
             int nb = lsq_div_up(J->n, LSQ_CMB_COLS);
             int grid = cap((long long)nb + epi.extra_blocks);
             LSQ_LAUNCH((k_combine<Epi>), dim3(grid), dim3(LSQ_NT), 0, c->stream, J->d_bpart, J->n,

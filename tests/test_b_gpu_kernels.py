@@ -16,13 +16,13 @@ pytestmark = pytest.mark.gpu
 
 # ------------------------------------------------------------------------------- kernels
 @pytest.mark.parametrize("window_rows", [None, 1024, 96])
-@pytest.mark.parametrize("plan", ["stream", "wave", "block", "ldswin", None])
+@pytest.mark.parametrize("plan", ["stream", "wave", "block", None])
 @pytest.mark.parametrize("m,n,density", [(3000, 200, 0.01), (500, 40, 0.5), (64, 3000, 0.02)])
 def test_sparse_products(ctx, plan, m, n, density, window_rows):
-    """All three launch plans, for the CSR rows, the CSC columns and (window_rows: forced small so
-    that small test matrices are cut into several windows) the row-window-blocked CSC of J'*y."""
-    for k in ("LSQ_PLAN_CSC", "LSQ_PLAN_CSR", "LSQ_PLAN_BCSC"):
-        if plan and not (plan == "ldswin" and k != "LSQ_PLAN_BCSC"):
+    """All three launch plans for the CSR rows and the CSC columns, and beside each of them (window_rows: forced small
+    so that small test matrices are cut into several LDS windows) the row-window-blocked CSC of J'*y."""
+    for k in ("LSQ_PLAN_CSC", "LSQ_PLAN_CSR"):
+        if plan:
             os.environ[k] = plan
         else:
             os.environ.pop(k, None)
@@ -40,7 +40,7 @@ def test_sparse_products(ctx, plan, m, n, density, window_rows):
         S.eliminate_zeros()
         J = lsq.DeviceMatrix(ctx, S)
     finally:
-        for k in ("LSQ_PLAN_CSC", "LSQ_PLAN_CSR", "LSQ_PLAN_BCSC", "LSQ_WINDOW_ROWS"):
+        for k in ("LSQ_PLAN_CSC", "LSQ_PLAN_CSR", "LSQ_WINDOW_ROWS"):
             os.environ.pop(k, None)
     A = O.Mat.from_scipy(S)
     rng = np.random.default_rng(1)
@@ -355,7 +355,7 @@ def test_ldiv_cholesky(ctx, n):
     _, nmul = sv.ldiv_(dxo, dy, lsq.DeviceVector(ctx, n, damp))
     st, xr, _, _ = O.ldiv(O.CHOLESKY, O.Mat(dense=D), y, damp)
     assert nmul == 1 and np.allclose(dxo.get(), xr, rtol=1e-9, atol=1e-12)
-    # n >= 128 (and at most one 64 x 64 upper tile per CU): the whole factorisation is one launch (k_chol_chain; k_chol_tiles when tiles + 1 > CUs)
+    # n >= 128 (and a CU for the chain and for every 64 x 64 upper tile): the whole factorisation is one launch (k_chol_chain)
     assert sv.info()["chol_path"] == ("blocked-one-launch" if n >= 128 else "blocked" if n >= 32 else "one-workgroup")
     sv = lsq.AllocatedSolver(J, lsq.Cholesky(), for_lm=False)  # pivoted (Dogleg)
     _, nmul = sv.ldiv_(dxo, dy)
@@ -364,7 +364,7 @@ def test_ldiv_cholesky(ctx, n):
 
 
 def test_cholesky_one_launch_is_repeatable(ctx):
-    """k_chol_chain / k_chol_tiles: workgroups hand tiles to each other inside ONE launch (epoch-tagged flags, bounded waits).  300 solves on
+    """k_chol_chain: workgroups hand tiles to each other inside ONE launch (epoch-tagged flags, bounded waits).  300 solves on
     one solver: every result equals the first bit for bit and no wait ever gave up (the path would fall back to
     'blocked' and stay there).  tools/chol_stress.py runs the same check for thousands of solves."""
     rng = np.random.default_rng(5)
@@ -380,6 +380,39 @@ def test_cholesky_one_launch_is_repeatable(ctx):
         sv.ldiv_(x, y, damp)
         assert sv.info()["chol_path"] == "blocked-one-launch"
         assert np.array_equal(x.get(), ref)
+
+
+def test_cholesky_one_launch_needs_a_cu_for_the_chain(ctx):
+    """The one-launch factorisation needs a CU for the chain workgroup beside one per 64 x 64 upper tile (lsq_cholesky_blocked:
+    tiles + 1 <= CUs).  On a 36-CU view of the device n = 512 (36 tiles) therefore takes the panel launches and n = 448
+    (28 tiles) the one launch; both solutions against the oracle, no give-ups."""
+    os.environ["LSQ_DEBUG_NUM_CUS"] = "36"
+    try:
+        c = lsq.Context(ctx.device)
+    finally:
+        del os.environ["LSQ_DEBUG_NUM_CUS"]
+    held = []                                 # (everything allocated on c is freed before c is closed, whatever happens)
+    try:
+        assert c.device_info()["num_cus"] == 36
+        for n, path in ((512, "blocked"), (448, "blocked-one-launch")):
+            rng = np.random.default_rng(30 + n)
+            m = 1541
+            D = rng.standard_normal((m, n))
+            y = rng.standard_normal(m)
+            damp = rng.random(n)
+            J = lsq.DeviceMatrix(c, D)
+            dy, dd, dxo = lsq.DeviceVector(c, m, y), lsq.DeviceVector(c, n, damp), lsq.DeviceVector(c, n)
+            sv = lsq.AllocatedSolver(J, lsq.Cholesky(), for_lm=True)
+            held += [J, dy, dd, dxo, sv]
+            sv.ldiv_(dxo, dy, dd)
+            assert sv.info()["chol_path"] == path
+            st, xr, _, _ = O.ldiv(O.CHOLESKY, O.Mat(dense=D), y, damp)
+            assert st == 0 and np.allclose(dxo.get(), xr, rtol=1e-9, atol=1e-12)
+        assert sum(c.fallback_stats().values()) == 0
+    finally:
+        for obj in reversed(held):
+            obj.free()
+        c.close()
 
 
 @pytest.mark.parametrize("cond,certified", [(1e1, True), (1e4, True), (1e7, False)])

@@ -30,18 +30,18 @@ from gpu_common import lsq
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(3000, 200, 0.01), (500, 40, 0.5), (64, 3000, 0.02)]
-PLANS = ("LSQ_PLAN_CSC", "LSQ_PLAN_CSR", "LSQ_PLAN_BCSC")
+PLANS = ("LSQ_PLAN_CSC", "LSQ_PLAN_CSR")
 
 
 def plan_env(plan, window=None):
-    env = {k: plan for k in PLANS if not (plan == "ldswin" and k != "LSQ_PLAN_BCSC")}      # (ldswin is a plan of the windowed J'y only)
+    env = {k: plan for k in PLANS}
     if window:
         env["LSQ_WINDOW_ROWS"] = str(window)
     return env
 
 
 LAYOUTS = {"default": {}}
-for _plan in ("stream", "wave", "block", "ldswin"):
+for _plan in ("stream", "wave", "block"):
     LAYOUTS[_plan] = plan_env(_plan)
     LAYOUTS[_plan + " window 96"] = plan_env(_plan, 96)
 LAYOUTS.update({"window 96": {"LSQ_WINDOW_ROWS": "96"},

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the sparse product kernels (HIP events, back-to-back launches).
-usage: spmv_bench.py [env-combo ...] where a combo is e.g. LSQ_WINDOW_ROWS=65536,LSQ_PLAN_BCSC=stream"""
+usage: spmv_bench.py [env-combo ...] where a combo is e.g. LSQ_PLAN_CSC=wave,LSQ_PLAN_CSR=stream"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -10,7 +10,7 @@ ctx = lsq.Context(0)
 m, n, pc = 1_000_000, 10000, 1000
 cp, rv, nz = lsq.synthetic.sparse_inputs(m, n, pc, 1)
 combos = sys.argv[1:] or [""]
-KEYS = ("LSQ_PLAN_CSC", "LSQ_PLAN_CSR", "LSQ_PLAN_BCSC", "LSQ_WINDOW_ROWS")
+KEYS = ("LSQ_PLAN_CSC", "LSQ_PLAN_CSR", "LSQ_WINDOW_ROWS")
 for combo in combos:
     for k in KEYS: os.environ.pop(k, None)
     for kv in filter(None, combo.split(",")):
