@@ -250,6 +250,11 @@ int lsq_solver_qr_panel(const lsq_solver *s, int *kind);
  * 4 like 2 with the whole factorisation in ONE launch (k_chol_chain: one resident workgroup per 64 x 64 upper tile
  * and one for the diagonal chain, n <= 1408; repeated as 2 if one of its bounded waits gives up) */
 int lsq_solver_chol_path(const lsq_solver *s, int *path);
+/* the same for LSMR(): which iteration driver ran the last solve.  0 none yet, 1 the reference-order kernel of small problems
+ * (lsq_exact.hip), 2 the four-launch iteration (k_lsmr_update: any handle, custom diagonal preconditioners, row blocks),
+ * 3 the three-launch iteration (k_lsmr_fused: both sliced layouts, one column window), 4 the operator-level recurrence of a
+ * general preconditioner (lsq_lsmr_general.hip).  Read-only; the tests use it to know which copy of the stopping rules ran. */
+int lsq_solver_lsmr_path(const lsq_solver *s, int *path);
 /* diagnostics of the last block solve: which path (0 none yet, 1 batched unpivoted LM, 2 batched pivoted Dogleg, 3 batched
  * per-block pivoted QR: LSQ_BLOCK_QR, block = -1, 4 bordered Schur, LM: lsq_blockdiag_bordered_create) and, after LSQ_ENOTPD /
  * LSQ_ERANK, the block that decided it (path 4: nblocks when the Schur factor of the shared columns failed) (else -1) */

@@ -158,6 +158,7 @@ def lib():
         "lsq_solver_qr_path": (i, [vp, c_ip]),
         "lsq_solver_qr_panel": (i, [vp, c_ip]),
         "lsq_solver_chol_path": (i, [vp, c_ip]),
+        "lsq_solver_lsmr_path": (i, [vp, c_ip]),
         "lsq_solver_blockdiag_path": (i, [vp, c_ip, c_ip]),
         "lsq_solver_blockdiag_ranks": (i, [vp, c_ip]),
         "lsq_solver_covariance": (i, [vp, vp, vp, vp, vp, c_ip]),

@@ -796,6 +796,8 @@ class AllocatedSolver:
         check(lib().lsq_solver_qr_path(self.h, C.byref(path)))
         cpath = C.c_int(0)
         check(lib().lsq_solver_chol_path(self.h, C.byref(cpath)))
+        lpath = C.c_int(0)
+        check(lib().lsq_solver_lsmr_path(self.h, C.byref(lpath)))
         panel = C.c_int(0)
         check(lib().lsq_solver_qr_panel(self.h, C.byref(panel)))
         bpath, bblock = C.c_int(0), C.c_int(-1)
@@ -808,6 +810,7 @@ class AllocatedSolver:
                                     4: "bordered-schur"}[bpath.value],
                     blockdiag_block=bblock.value, block_ranks=block_ranks,
                     lsmr_iter=it.value, lsmr_istop=st.value, qr_rank=rk.value,
+                    lsmr_path={0: None, 1: "reference-order", 2: "four-launch", 3: "three-launch", 4: "general"}[lpath.value],
                     qr_panel={0: None, 1: "householder-steps", 2: "cholqr2"}[panel.value],
                     qr_path={0: None, 1: "one-stage", 2: "two-stage-pivoted", 3: "two-stage-certified"}[path.value],
                     chol_path={0: None, 1: "one-workgroup", 2: "blocked", 3: "blocked-certified", 4: "blocked-one-launch"}[cpath.value])

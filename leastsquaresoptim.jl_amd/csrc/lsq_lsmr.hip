@@ -1039,11 +1039,13 @@ int lsq_lsmr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, double *d_damp,
             return LSQ_EARG;
         }
         LSQ_TRY(lsq_lsmr_general_solve(s, J, d_y, d_damp, d_x, nmul));
+        s->last_lsmr_path = 4;
         return tail && tail->fn ? tail->fn(nullptr, tail->user) : LSQ_OK;
     }
     const bool sharded = s->row_cb != nullptr;     // J is a row block: the adjoint product is summed over the ranks
     if (lsq_small_mat(J) && !s->precond_cb && !sharded) {   // reference-order kernel
         LSQ_TRY(lsq_lsmr_exact_solve(s, J, d_y, d_damp, d_x, nmul));
+        s->last_lsmr_path = 1;
         return tail && tail->fn ? tail->fn(nullptr, tail->user) : LSQ_OK;
     }
     LsmrWork W;
@@ -1096,6 +1098,7 @@ int lsq_lsmr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, double *d_damp,
     LSQ_TRY(W.fused ? lsmr_run_fused(W, pred, r) : lsmr_run_four(W, pred, r));
     s->last_iter = r.it;
     s->last_istop = r.istop;
+    s->last_lsmr_path = W.fused ? 3 : 2;
     if (nmul) *nmul = 2 * r.it;  // lsmr.jl:236 ch.mvps
     if (W.dynamic && pred.t2_prev > 0.0) s->lsmr_ratio2 = pred.ratio2;
     if (tail && tail->fn && !r.tail_ran) LSQ_TRY(tail->fn(nullptr, tail->user));

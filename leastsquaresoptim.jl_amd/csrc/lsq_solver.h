@@ -64,6 +64,7 @@ struct lsq_solver {
     unsigned f3_tag = 0;       // tag of the newest in-launch record of k_lsmr_fused
     unsigned epoch = 0;
     int last_iter = 0, last_istop = 0;
+    int last_lsmr_path = 0;    // lsq_solver_lsmr_path
     // row-sharded single problem (lsq_options.row_allreduce): J is this rank's row block; J'u and sum(u^2) are summed over
     // the ranks in d_xbuf (n + 1 doubles) between the adjoint product and its epilogue
     int (*row_cb)(double *, int, void *, void *) = nullptr;

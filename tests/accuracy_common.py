@@ -59,6 +59,12 @@ def bound(e_ref, k):
     return FACTOR * max(float(e_ref), min(max(16, k), FLOOR_CAP) * UNIT)
 
 
+def lsmr_bound(e_ref, n, iters):
+    """The same rule for an LSMR iterate after `iters` iterations (tests/test_k_gpu_lsmr_stops.py): the floor is scaled by the
+    iteration count, because every iteration adds a product's worth of rounding to the recurrence."""
+    return FACTOR * max(float(e_ref), min(max(16, n), FLOOR_CAP) * UNIT * iters)
+
+
 def accepted(e_dev, e_ref, k):
     return bool(np.isfinite(e_dev)) and float(e_dev) <= bound(e_ref, k)
 

@@ -3,6 +3,8 @@ random sparse operands and the trajectory runners / comparator against the oracl
 differs: tree reductions vs the serial loops of the reference):
     kernels                         |err| <= 1e-12 * scale
     one linear solve (ldiv!)        rel 1e-9 (direct), LSMR: identical iteration count, rel 1e-8
+                                    (stop code, counts and the tier's accuracy rule per stopping rule and driver:
+                                    tests/test_k_gpu_lsmr_stops.py, cases certified by tests/test_lsmr_stops_host.py)
     trust-region trajectories       small problems run the reference-order kernels (lsq_exact.hip):
                                     identical iteration / f / g / mul counts, accept pattern and inner
                                     iteration counts on the whole reference grid, iterates equal to
