@@ -458,17 +458,24 @@ static int sumsq_to_slot(lsq_ctx *c, bool exact, long long n, const double *x, i
 // sum rides in the residual kernel's epilogue (no second pass over the m-vector: 8 MB and a launch less per iteration at C4)
 static int model_f(double *out, const double *x, void *user);
 static int model_g(lsq_mat *J, const double *x, void *user);
+// mirror: the caller expects model_pair_tail to read `out` next -- the pass leaves it in slice order too (no k_sell_perm_rows)
 static int model_f_sumsq(void *user, double *out, const double *x, int ctr, double *d_out, LsqSlotPublish pub, bool *done,
-                         const int *skip = nullptr);
+                         const int *skip = nullptr, bool mirror = false);
+// the start point of a solve on the model's sliced rows: tanh(x0), 1 - tanh(x0)^2 and the first non-finite index of x0 (-> slot)
+// in one launch; *done tells whether it applied (else nothing was launched)
+static int model_start_point(void *user, const double *x, double *d_nonfin, bool *done);
+// an error return between model_start_point and the g! that would have consumed its factors: nothing stays recorded
+static void model_forget_point(void *user);
 // predicted residual |J dx - f|^2 AND f!(x_trial) with its sum of squares in ONE pass over the model's matrix
 // (k_sell_rows_pair, lsq_sell.h); *done tells whether it applied (else nothing was launched: the caller takes the two passes)
-// sg (optional): also queue the NEXT iteration's gradient + colsumabs2 pass behind it, guarded by the acceptance test the
-// kernel takes on the device (lsq_sparse_grad_colsum_spec); sg->launched tells whether that pass was queued
+// sg (optional): also queue the NEXT iteration's gradient + colsumabs2 pass behind it, guarded by the acceptance and convergence
+// tests the kernel takes on the device (lsq_sparse_grad_colsum_spec); sg->launched tells whether that pass was queued
 struct SpecGrad {
     int *gate;          // this pass's skip word (non-zero until the pair kernel clears it)
     double ssr;         // the current sum of squares (what the host will test rho against)
     double *grad;       // where the gradient goes
     bool launched;
+    double xtol, ftol, gtol;    // the loop's tolerances (what the host's assess() will test with)
 };
 static int model_pair_tail(void *user, lsq_mat *J, const double *dx, const double *fcur, double *ftrial, const double *xt,
                            double *slot_pred, double *slot_trial, LsqSlotPublish pub, const int *skip, bool *done,
@@ -476,10 +483,10 @@ static int model_pair_tail(void *user, lsq_mat *J, const double *dx, const doubl
 // buffers for tanh(xt) and 1 - tanh(xt)^2 when the model's next f!(., xt) can take them from the step kernel (else nulls)
 static void model_trial_buffers(void *user, const double *xt, double **t_out, double **s_out);
 static int f_then_sumsq(lsq_ctx *c, bool exact, lsq_f_callback f, void *user, long long m, double *out, const double *x, int ctr,
-                        double *d_out, LsqSlotPublish pub = LsqSlotPublish(), const int *skip = nullptr) {
+                        double *d_out, LsqSlotPublish pub = LsqSlotPublish(), const int *skip = nullptr, bool mirror = false) {
     if (!exact && f == model_f) {
         bool fused = false;
-        if (model_f_sumsq(user, out, x, ctr, d_out, pub, &fused, skip) != 0) {
+        if (model_f_sumsq(user, out, x, ctr, d_out, pub, &fused, skip, mirror) != 0) {
             lsq_set_error("user callback reported failure");
             return LSQ_ECALLBACK;
         }
@@ -730,8 +737,17 @@ struct IterateGuard {
 // The head of both loops -- f!(fcur, x0), ssr = sum(abs2, fcur), check_isfinite(x0) (levenberg_marquardt.jl:58-60,74; dogleg.jl:66-68,
 // 79) -- behind ONE host hand-over instead of two (rounds 1-4: the sum and the check each waited for the device: ~40 us per
 // solve at C4).  The built-in model's sum rides in its residual kernel.  Small problems keep the reference-order sums.
+// The kernel that forms the sum hands both scalars to the host itself.  The built-in model on its sliced rows starts with ONE
+// n-length launch (the check, tanh(x0) for f! and the factors of the first g!); pair_next: the loop's tail will be
+// model_pair_tail, which reads fcur in slice order -- the residual pass leaves that mirror behind as well.
+// ahead (optional, taken only behind that one-launch start): work the caller queues BEFORE the host waits for the two scalars,
+// so that the device does not stand idle during the hand-over -- the caller undoes its bookkeeping if x0 turns out non-finite.
+struct StartAhead {
+    int (*fn)(void *);
+    void *user;
+};
 static int start_residual(lsq_ctx *c, lsq_mat *J, lsq_f_callback f, void *user, double *fcur, const double *x, double *ssr,
-                          int *nonfinite_at) {
+                          int *nonfinite_at, bool pair_next = false, const StartAhead *ahead = nullptr) {
     const int m = J->m, n = J->n;
     if (lsq_small_mat(J) || lsq_small_vec(m) || m <= 0) {
         CB(f(fcur, x, user));
@@ -739,10 +755,18 @@ static int start_residual(lsq_ctx *c, lsq_mat *J, lsq_f_callback f, void *user, 
         return lsq_first_nonfinite(c, n, x, nonfinite_at);
     }
     static_assert(SL_TRIAL == SL_NONFIN + 1, "the two scalars of the loop head travel together");
-    LSQ_TRY(lsq_first_nonfinite_to_slot(c, n, x, c->d_slots + SL_NONFIN));
-    LSQ_TRY(f_then_sumsq(c, false, f, user, m, fcur, x, 7, c->d_slots + SL_TRIAL));
+    bool head = false;
+    if (f == model_f && model_start_point(user, x, c->d_slots + SL_NONFIN, &head) != 0) return LSQ_EHIP;
+    if (!head) LSQ_TRY(lsq_first_nonfinite_to_slot(c, n, x, c->d_slots + SL_NONFIN));
+    const LsqSlotPublish pub = lsq_slots_ticket(c, SL_NONFIN, 2);
     double sl[2];
-    LSQ_TRY(lsq_read_slots(c, SL_NONFIN, 2, sl));
+    int st = f_then_sumsq(c, false, f, user, m, fcur, x, 7, c->d_slots + SL_TRIAL, pub, nullptr, pair_next);
+    if (st == LSQ_OK && head && ahead) st = ahead->fn(ahead->user);
+    if (st == LSQ_OK) st = lsq_wait_slots(c, SL_NONFIN, 2, pub.seq, sl);
+    if (st != LSQ_OK || (int)sl[0] >= 0) {
+        if (head) model_forget_point(user);     // (no g! will follow at this x0)
+        if (st != LSQ_OK) return st;
+    }
     *nonfinite_at = (int)sl[0];
     *ssr = sl[1];
     return LSQ_OK;
@@ -769,8 +793,31 @@ static int optimize_lm_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat 
     // row-sharded single problem: J, fcur, ftrial are this rank's rows; sums over residuals are completed across the ranks
     // by the hook (a device buffer, in place, ordered on the stream) before the host reads them
     const bool sharded = o->row_allreduce != nullptr;
+    // The first g! and the gradient + colsumabs2 pass of its Jacobian are queued behind the start residual BEFORE the host waits
+    // for ssr and the check of x0 (the device used to stand idle for that round trip): the built-in model with LSMR.  A
+    // non-finite x0 still leaves at the top of the first iteration, with the counts of a loop that never called g!; the
+    // colsumabs2 formed for those factors is forgotten.
+    struct AheadCtx { lsq_g_callback g; lsq_mat *J; const double *x; void *user; const double *fcur; double *grad; bool g_done, grad_done; }
+        ah{g, J, x, user, fcur, b.grad, false, false};
+    const StartAhead ahead{[](void *p) -> int {
+        AheadCtx &a = *(AheadCtx *)p;
+        LSQ_TRY(call_g(a.g, a.J, a.x, a.user));
+        a.g_done = true;
+        if (a.J->colsum_version != a.J->version && lsq_can_fuse_grad_colsum(a.J)) {
+            LSQ_TRY(lsq_sparse_grad_colsum(a.J, a.fcur, a.grad));
+            a.grad_done = true;
+        }
+        return LSQ_OK;
+    }, &ah};
+    const bool ahead_ok = f == model_f && g == model_g && sv->kind == LSQ_LSMR && o->iterations > 0;
     if (sharded) CB(f(fcur, x, user));
-    else LSQ_TRY(start_residual(c, J, f, user, fcur, x, &ssr, &nonfinite_at));
+    else {
+        const int st = start_residual(c, J, f, user, fcur, x, &ssr, &nonfinite_at,
+                                      sv->kind == LSQ_LSMR && !o->h_lower && !o->h_upper && !lsq_small_mat(J),
+                                      ahead_ok ? &ahead : nullptr);
+        if (ah.g_done && (st != LSQ_OK || nonfinite_at >= 0)) lsq_sparse_colsum_forget(J);
+        LSQ_TRY(st);
+    }
     f_calls++;
     auto rows_sum = [&](double *d_buf, int count) -> int {
         if (o->row_allreduce(d_buf, count, (void *)c->stream, o->row_allreduce_user) != 0) {
@@ -824,12 +871,14 @@ static int optimize_lm_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat 
             return LSQ_ENONFINITE;
         }
         if (need_jac) {
-            LSQ_TRY(call_g(g, J, x, user));
+            if (!ah.g_done) LSQ_TRY(call_g(g, J, x, user));     // (the first one may be queued already: see ahead)
+            ah.g_done = false;
             g_calls++;
             need_jac = false;
         }
         // a fresh Jacobian needs colsumabs2 (:82) and J'f (:102): one pass over J gives both
-        bool have_grad = false;
+        bool have_grad = ah.grad_done;
+        ah.grad_done = false;
         if (spec_grad_ready) {      // ... and that pass has already run behind the previous iteration's tail
             lsq_sparse_grad_colsum_adopt(J);
             have_grad = true;
@@ -900,9 +949,9 @@ static int optimize_lm_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat 
             lsq_ctx *c; lsq_mat *J; LoopBuffers *b; lsq_f_callback f; void *user;
             const double *x, *fcur; double *xt, *ftrial;
             int m, n, gn; bool is_model; LsqSlotPublish pub; int launched;
-            bool want_spec; double ssr; bool spec_launched; bool *spec_pending;
+            bool want_spec; double ssr; bool spec_launched; bool *spec_pending; const lsq_options *o;
         } tc{c, J, &b, f, user, x, fcur, xt, ftrial, m, n, gn, !exact && f == model_f, LsqSlotPublish(), 0, spec_ok, ssr, false,
-             &spec_pending};
+             &spec_pending, o};
         auto tail_fn = [](const int *skip, void *u) -> int {
             TailCtx &t = *(TailCtx *)u;
             lsq_ctx *c = t.c;
@@ -912,9 +961,9 @@ static int optimize_lm_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat 
                                lsq_ctr(c, 5), c->d_slots + SL_DX, c->d_slots + SL_NONFIN, t_out, s_out, skip);   // :106
             LSQ_HIP(hipGetLastError());
             // the last kernel of the iteration hands the scalars to the host
-            t.pub = lsq_slots_ticket(c, SL_GRAD, 6);      // (the sixth: the device's own acceptance decision, k_sell_rows_pair)
+            t.pub = lsq_slots_ticket(c, SL_GRAD, 6);      // (the sixth: whether the device let the queued pass run, k_sell_rows_pair)
             bool pair = false;
-            SpecGrad sg{t.want_spec ? next_gate(c, *t.b) : nullptr, t.ssr, t.b->grad, false};
+            SpecGrad sg{t.want_spec ? next_gate(c, *t.b) : nullptr, t.ssr, t.b->grad, false, t.o->x_tol, t.o->f_tol, t.o->g_tol};
             if (t.is_model && model_pair_tail(t.user, t.J, t.b->dx, t.fcur, t.ftrial, t.xt, c->d_slots + SL_PRED, c->d_slots + SL_TRIAL,
                                               t.pub, skip, &pair, &sg) != 0) {
                 lsq_set_error("user callback reported failure");
@@ -994,14 +1043,17 @@ static int optimize_lm_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat 
         const double pred_red = std::fabs(ssr - predicted_ssr);
         const double rho = pred_red > 0 ? (ssr - trial_ssr) / pred_red : 0.0;   // :118-119
         const bool accepted = rho > MIN_STEP_QUALITY;                           // :122 (strict)
-        // the gradient + colsumabs2 pass of the next Jacobian was queued behind the tail and took the same decision on the device
-        // -- adopted only if the device's decision (the sixth scalar) is the host's; should they ever differ, a pass that ran for a
-        // step the host refuses has overwritten the handle's colsumabs2 with another Jacobian's: forget it
-        const bool dev_accepted = spec_launched && sl[5] != 0.0;
-        spec_grad_ready = spec_launched && accepted && dev_accepted;
-        if (spec_launched && dev_accepted && !accepted) lsq_sparse_colsum_forget(J);
-        spec_pending = false;       // (ruled on: adopted at the head of the next iteration, forgotten, or never run on the device)
         converged = assess(maxabs_dx, maxabs_gr, ssr, trial_ssr, o->x_tol, o->f_tol, o->g_tol, accepted, &xc, &fc, &gc);
+        // the gradient + colsumabs2 pass of the next Jacobian was queued behind the tail, and the device let it run only behind a
+        // step it found accepted and not converged (the sixth scalar: "the pass ran").  The host's own decision rules: adopted only
+        // if the host, too, goes on from an accepted step; a pass that ran where the host does not go on (or refuses the step) has
+        // overwritten the handle's colsumabs2 with a Jacobian nobody installs: forget it.  Where the host goes on and the pass did
+        // not run, the ordinary pass at the head of the next iteration does.
+        const bool dev_ran = spec_launched && sl[5] != 0.0;
+        const bool host_goes_on = accepted && !converged;
+        spec_grad_ready = dev_ran && host_goes_on;
+        if (dev_ran && !host_goes_on) lsq_sparse_colsum_forget(J);
+        spec_pending = false;       // (ruled on: adopted at the head of the next iteration, forgotten, or never run on the device)
         if (accepted) {
             std::swap(fcur, ftrial);                                            // copyto!(fcur, ftrial)
             std::swap(x, xt);
@@ -1358,6 +1410,16 @@ struct EpiResidualSq {  // out = A t - b, and sum(out.^2) -> slot (+ the iterati
     }
 };
 
+// ... and the same residual in the SLICE ORDER of the sliced rows (what k_sell_rows_pair reads: SellPairEpi), stored by the lane
+// that formed the row's sum: out_perm[s * 64 + lane] = dot - b_perm[s * 64 + lane], the bits of out[row]
+struct EpiResidualSqPerm : EpiResidualSq {
+    const double *b_perm;
+    double *out_perm;
+    using has_slice_out = void;
+    __device__ double slice_pre(size_t pidx) const { return b_perm[pidx]; }
+    __device__ void slice_post(size_t pidx, double dot, double bi) const { out_perm[pidx] = dot - bi; }
+};
+
 // column scaling of a column-segmented value array (CSC nzval or dense columns)
 __global__ void __launch_bounds__(LSQ_NT)
 k_scale_cols(int n, const int *__restrict__ colptr, int m_dense, const double *__restrict__ A,
@@ -1386,13 +1448,24 @@ k_scale_csr(long long nnz, const int *__restrict__ colidx, const double *__restr
     for (long long k = blockIdx.x * (long long)LSQ_NT + threadIdx.x; k < nnz; k += (long long)gridDim.x * LSQ_NT)
         out[k] = A[k] * sfac[colidx[k]];
 }
+// the start point of a solve: t = tanh(x), s = 1 - tanh(x)^2 (k_tanh and k_sfac, the same expressions) and check_isfinite(x)
+// (k_first_nonfinite, the same code) in one launch
 __global__ void __launch_bounds__(LSQ_NT) k_tanh_sfac(int n, const double *__restrict__ x, double *__restrict__ t,
-                                                      double *__restrict__ s) {
+                                                      double *__restrict__ s, double *partials, unsigned *counter,
+                                                      double *out_nonfin) {
+    __shared__ double sh[LSQ_NT / 64];
+    double code = 0.0;
     for (int i = blockIdx.x * LSQ_NT + threadIdx.x; i < n; i += gridDim.x * LSQ_NT) {
-        const double v = tanh(x[i]);
+        const double xi = x[i];
+        const double v = tanh(xi);
         t[i] = v;
         s[i] = 1.0 - v * v;
+        if (!isfinite(xi) && code == 0.0) code = 1e15 - (double)(i + 1);
     }
+    const double bv = block_max<LSQ_NT>(code, sh);
+    grid_reduce<LSQ_NT, true>(bv, partials, counter, gridDim.x, sh, [=](double m) {
+        *out_nonfin = (m == 0.0) ? -1.0 : (1e15 - m) - 1.0;
+    });
 }
 __global__ void __launch_bounds__(LSQ_NT) k_sfac(int n, const double *__restrict__ x, double *__restrict__ s) {
     for (int i = blockIdx.x * LSQ_NT + threadIdx.x; i < n; i += gridDim.x * LSQ_NT) {
@@ -1497,9 +1570,54 @@ static void model_trial_buffers(void *user, const double *xt, double **t_out, do
     }
 }
 
+static int model_start_point(void *user, const double *x, double *d_nonfin, bool *done) {
+    lsq_model *md = (lsq_model *)user;
+    lsq_ctx *c = md->ctx;
+    lsq_mat *J = md->J;
+    *done = false;
+    md->tanh_x = md->sfac_x = nullptr;
+    if (!(J->kind == LSQ_MAT_CSC && J->srows.active) || J->n <= 0) return 0;
+    LSQ_LAUNCH(k_tanh_sfac, dim3(ngrid(c, J->n)), dim3(LSQ_NT), 0, c->stream, J->n, x, md->d_t, md->d_sspec, c->d_partials,
+               lsq_ctr(c, 0), d_nonfin);
+    if (hipGetLastError() != hipSuccess) return 1;
+    md->tanh_x = md->sfac_x = x;      // (as model_trial_buffers records them for the step kernel)
+    *done = true;
+    return 0;
+}
+static void model_forget_point(void *user) {
+    lsq_model *md = (lsq_model *)user;
+    md->tanh_x = md->sfac_x = nullptr;
+}
+
+// does model_pair_tail apply to this handle (its conditions on the model and the layout; the caller adds those on the vectors)
+static bool model_pair_applies(const lsq_model *md, const lsq_mat *J) {
+    return md->fused && J == md->J && J->kind == LSQ_MAT_CSC && J->srows.active && J->srows.ncw == 1 && J->d_colscale &&
+           J->n <= LSQ_PAIR_X_MAX && !getenv("LSQ_NO_PAIR_TAIL");
+}
+// the slice-order buffers of model_pair_tail: b once per model, two mirrors of residual vectors.  false: they could not be
+// allocated (the callers take the paths that do without)
+static bool model_perm_ready(lsq_model *md) {
+    if (md->d_b_perm) return true;
+    lsq_ctx *c = md->ctx;
+    const LsqSell &S = md->J->srows;
+    const size_t plen = (size_t)S.nslices * 64;
+    const int pgrid = std::max(1, std::min(lsq_div_up((long long)plen, LSQ_NT), c->num_cus * 8));
+    double *pb = nullptr, *p0 = nullptr, *p1 = nullptr;     // (all three or none: a partial set must not look initialised)
+    if (hipMalloc(&pb, plen * sizeof(double)) != hipSuccess || hipMalloc(&p0, plen * sizeof(double)) != hipSuccess ||
+        hipMalloc(&p1, plen * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        hipFree(pb); hipFree(p0); hipFree(p1);
+        return false;
+    }
+    md->d_b_perm = pb; md->d_perm[0] = p0; md->d_perm[1] = p1;
+    LSQ_LAUNCH(k_sell_perm_rows<0>, dim3(pgrid), dim3(LSQ_NT), 0, c->stream, sell_dev(S), S.wrows, S.nslices, (const double *)md->d_b,
+               md->d_b_perm);
+    return true;
+}
+
 // f! + sum(abs2, out) in one pass (sliced rows only; *done tells whether it applied)
 static int model_f_sumsq(void *user, double *out, const double *x, int ctr, double *d_out, LsqSlotPublish pub, bool *done,
-                         const int *skip) {
+                         const int *skip, bool mirror) {
     lsq_model *md = (lsq_model *)user;
     lsq_ctx *c = md->ctx;
     lsq_mat *J = md->J;
@@ -1507,13 +1625,20 @@ static int model_f_sumsq(void *user, double *out, const double *x, int ctr, doub
     if (!(J->kind == LSQ_MAT_CSC && J->srows.active)) return model_f(out, x, user);
     model_perm_invalidate(md, out);
     EpiResidualSq e{skip, 0, md->d_b, out, c->d_partials, lsq_ctr(c, ctr), d_out, pub};
-    const bool have_tanh = md->tanh_x == x;   // k_step formed tanh(x) while it wrote x
+    const bool have_tanh = md->tanh_x == x;   // k_step (or k_tanh_sfac at the start point) formed tanh(x)
     md->tanh_x = nullptr;
     if (!have_tanh) {
         md->sfac_x = nullptr;
         LSQ_LAUNCH(k_tanh, dim3(ngrid(c, J->n)), dim3(LSQ_NT), 0, c->stream, J->n, x, md->d_t);
     }
-    if (launch_sell_rows(J, nullptr, md->d_t, e, md->fused ? nullptr : md->d_Acsr) != LSQ_OK) return 1;
+    if (mirror && !skip && model_pair_applies(md, J) && model_perm_ready(md)) {
+        EpiResidualSqPerm ep;
+        static_cast<EpiResidualSq &>(ep) = e;
+        ep.b_perm = md->d_b_perm;
+        ep.out_perm = md->d_perm[0];
+        if (launch_sell_rows(J, nullptr, md->d_t, ep, nullptr) != LSQ_OK) return 1;
+        md->perm_of[0] = out;       // (model_pair_tail finds it there; perm_of[1] names another vector or nothing: `out` was invalidated)
+    } else if (launch_sell_rows(J, nullptr, md->d_t, e, md->fused ? nullptr : md->d_Acsr) != LSQ_OK) return 1;
     *done = true;
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
@@ -1525,9 +1650,7 @@ static int model_pair_tail(void *user, lsq_mat *J, const double *dx, const doubl
     *done = false;
     // the column-scaled handle on the one-window sliced rows (J = A diag(s): both products stream the same A), both gather
     // vectors resident in LDS, tanh(x_trial) already formed by the step kernel
-    if (!(md->fused && J == md->J && J->kind == LSQ_MAT_CSC && J->srows.active && J->srows.ncw == 1 && J->d_colscale &&
-          J->n <= LSQ_PAIR_X_MAX && md->tanh_x == xt) || getenv("LSQ_NO_PAIR_TAIL"))
-        return 0;
+    if (!(model_pair_applies(md, J) && md->tanh_x == xt)) return 0;
     const LsqSell &S = J->srows;
     const int nxpad = (J->n + 1) & ~1;
     // (two gather vectors; after a block's stream their LDS is the output window of its LSQ_SELL_ROWS_MAX rows)
@@ -1537,18 +1660,7 @@ static int model_pair_tail(void *user, lsq_mat *J, const double *dx, const doubl
     // produced fcur was accepted, else permuted now); the other slot takes this launch's trial residual
     const size_t plen = (size_t)S.nslices * 64;
     const int pgrid = std::max(1, std::min(lsq_div_up((long long)plen, LSQ_NT), c->num_cus * 8));
-    if (!md->d_b_perm) {
-        double *pb = nullptr, *p0 = nullptr, *p1 = nullptr;     // (all three or none: a partial set must not look initialised)
-        if (hipMalloc(&pb, plen * sizeof(double)) != hipSuccess || hipMalloc(&p0, plen * sizeof(double)) != hipSuccess ||
-            hipMalloc(&p1, plen * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            hipFree(pb); hipFree(p0); hipFree(p1);
-            return 0;                                           // (the caller takes the two-pass tail)
-        }
-        md->d_b_perm = pb; md->d_perm[0] = p0; md->d_perm[1] = p1;
-        LSQ_LAUNCH(k_sell_perm_rows<0>, dim3(pgrid), dim3(LSQ_NT), 0, c->stream, sell_dev(S), S.wrows, S.nslices, (const double *)md->d_b,
-                   md->d_b_perm);
-    }
+    if (!model_perm_ready(md)) return 0;                        // (the caller takes the two-pass tail)
     int k = md->perm_of[0] == fcur ? 0 : (md->perm_of[1] == fcur ? 1 : -1);
     if (k < 0) {
         k = 0;
@@ -1562,7 +1674,8 @@ static int model_pair_tail(void *user, lsq_mat *J, const double *dx, const doubl
     const bool spec = sg && sg->gate && md->sfac_x == xt;
     SellPairEpi e{skip, md->d_perm[k], md->d_b_perm, ftrial, md->d_perm[1 - k], c->d_partials, c->d_partials + 4096, lsq_ctr(c, 7),
                   slot_pred, slot_trial, pub, spec ? sg->gate : nullptr, spec ? sg->ssr : 0.0, MIN_STEP_QUALITY,
-                  c->d_slots + SL_SSR};
+                  c->d_slots + SL_SSR, c->d_slots + SL_DX, c->d_slots + SL_GRAD, spec ? sg->xtol : 0.0, spec ? sg->ftol : 0.0,
+                  spec ? sg->gtol : 0.0};
     LSQ_LAUNCH(k_sell_rows_pair<0>, dim3(grid), dim3(LSQ_BIG_NT), lds, c->stream, sell_dev(S), S.wrows, J->m, dx, J->d_colscale,
                (const double *)md->d_t, J->n, nxpad, e);
     *done = true;

@@ -181,8 +181,15 @@ __device__ __forceinline__ SellSliceRef sell_slice_ref(const SellDev &S, int s, 
     }
     return r;
 }
-template <bool SQ, class Out>
-__device__ __forceinline__ void sell_wave_slices(const SellDev &S, int s0, int s1, int wv, int lane, const double *xl, Out out) {
+//   `hook` (optional) also sees a lane's sum at its SLICE-ORDER index s * 64 + lane (what k_sell_rows_pair reads and writes):
+//   pre(pidx) is requested before the slice's stream, post(pidx, sum, pre) follows the lane's result.
+struct SellNoSliceHook {
+    __device__ __forceinline__ double pre(size_t) const { return 0.0; }
+    __device__ __forceinline__ void post(size_t, double, double) const {}
+};
+template <bool SQ, class Out, class Hook = SellNoSliceHook>
+__device__ __forceinline__ void sell_wave_slices(const SellDev &S, int s0, int s1, int wv, int lane, const double *xl, Out out,
+                                                 Hook hook = Hook()) {
     constexpr int NW = LSQ_BIG_NT / 64;
     int s = s0 + wv;
     SellSliceRef A = sell_slice_ref(S, s, s1, lane);
@@ -192,11 +199,23 @@ __device__ __forceinline__ void sell_wave_slices(const SellDev &S, int s0, int s
         A = sell_slice_ref(S, s + NW, s1, lane);
         const size_t oa = (size_t)a.sm.x + lane * 2;
         const unsigned pos = a.inf & LSQ_SELL_POS_MASK;
+        const size_t pidx = (size_t)s * 64 + lane;
+        const double hp = hook.pre(pidx);                   // (coalesced; in flight during the stream)
         double sum = 0.0, sq = 0.0;
         sell_lane_sum<SQ>(S.val + oa, S.idx16 + oa, a.sm.y, (int)(a.inf >> LSQ_SELL_POS_BITS), xl, sum, sq, lane);
-        if (pos != LSQ_SELL_POS_MASK) out(pos, sum, sq);
+        if (pos != LSQ_SELL_POS_MASK) {
+            out(pos, sum, sq);
+            hook.post(pidx, sum, hp);
+        }
     }
 }
+// an epilogue that wants its rows in slice order as well (has_slice_out): slice_pre / slice_post, see sell_wave_slices
+template <class Epi>
+struct SellEpiSliceHook {
+    const Epi &epi;
+    __device__ __forceinline__ double pre(size_t pidx) const { return epi.slice_pre(pidx); }
+    __device__ __forceinline__ void post(size_t pidx, double sum, double p) const { epi.slice_post(pidx, sum, p); }
+};
 
 // ---- J*x: dot of every row with x, then the epilogue on (row, dot) in row order ----------------
 // xscale (or null): the matrix is the stored values times diag(xscale) -- a COLUMN-SCALED Jacobian J = V diag(s) whose scaled
@@ -241,7 +260,11 @@ __global__ void __launch_bounds__(LSQ_BIG_NT) k_sell_rows(SellDev S, int wrows, 
             for (int q = 0; q < Q; ++q) pre[q] = epi.pre(base + min(tid + q * LSQ_BIG_NT, rows - 1));
         }
         // (the barrier inside: x staged / the previous window's epilogue is done with yw)
-        sell_wave_slices<false>(S, s0, s1, wv, lane, xl, [&](unsigned pos, double sum, double) { yw[pos] = sum; });
+        if constexpr (EpiHasSliceOut<Epi>::value)
+            sell_wave_slices<false>(S, s0, s1, wv, lane, xl, [&](unsigned pos, double sum, double) { yw[pos] = sum; },
+                                    SellEpiSliceHook<Epi>{epi});
+        else
+            sell_wave_slices<false>(S, s0, s1, wv, lane, xl, [&](unsigned pos, double sum, double) { yw[pos] = sum; });
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
@@ -341,13 +364,16 @@ struct SellPairEpi {
     unsigned *counter;          // ticket slot of grid_reduce
     double *slot_a, *slot_b;
     LsqSlotPublish pub;         // the iteration's scalars -> host once both sums are final
-    // LM's acceptance test taken on the device as well (levenberg_marquardt.jl:118-122, the host's own expression on the same
-    // doubles): *gate = 0 if the step will be accepted, 1 if not -- the skip word of the NEXT iteration's gradient pass, which
-    // is queued behind this kernel before the host has seen the scalars (null: no such pass is queued)
+    // LM's acceptance test AND its convergence test taken on the device as well (levenberg_marquardt.jl:118-122 and utils.jl:7-31,
+    // the host's own expressions on the same doubles): *gate = 0 if the step will be accepted and the loop goes on, 1 if not --
+    // the skip word of the NEXT iteration's gradient pass, which is queued behind this kernel before the host has seen the
+    // scalars (null: no such pass is queued).  A pass behind a converging step would run for a Jacobian nobody forms.
     int *gate;
     double ssr, min_quality;
-    double *slot_gate;          // the decision as a scalar (1.0 accepted / 0.0 not) among the published ones: the host adopts the
-                                // queued pass only if the device took the decision the host takes
+    double *slot_gate;          // "the pass runs" as a scalar (1.0 / 0.0) among the published ones: the host adopts the queued
+                                // pass only if it ran AND the host's own decision is "accepted, not converged"
+    const double *slot_dx, *slot_gr;    // max |dx| and max |gradient| of this iteration (final before this kernel starts)
+    double xtol, ftol, gtol;
 };
 // dst[s * 64 + lane] = src[row owned by lane of slice s] (0 for lanes without a row): an m-vector in slice order
 template <int = 0>
@@ -459,8 +485,12 @@ __global__ void __launch_bounds__(LSQ_BIG_NT) k_sell_rows_pair(SellDev S, int wr
             const double pred_red = fabs(e.ssr - total_a);
             const double rho = pred_red > 0 ? (e.ssr - total_b) / pred_red : 0.0;
             const bool acc = rho > e.min_quality;
-            *e.gate = acc ? 0 : 1;
-            *e.slot_gate = acc ? 1.0 : 0.0;
+            // (the if/elseif chain of the host's assess(): which flag fires does not matter here, only whether one does)
+            const bool conv = (acc && fabs(total_b - e.ssr) <= e.ftol * (fabs(e.ssr) + e.ftol)) || *e.slot_dx <= e.xtol ||
+                              *e.slot_gr <= e.gtol;
+            const bool go = acc && !conv;
+            *e.gate = go ? 0 : 1;
+            *e.slot_gate = go ? 1.0 : 0.0;
         }
         if (e.pub.count > 0) {
             for (int i = 0; i < e.pub.count; ++i) {

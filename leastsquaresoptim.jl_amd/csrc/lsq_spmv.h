@@ -246,6 +246,11 @@ template <class E, class = void>
 struct EpiHasPre : std::false_type {};
 template <class E>
 struct EpiHasPre<E, std::void_t<typename E::has_pre>> : std::true_type {};
+// slice_pre(pidx) / slice_post(pidx, dot, pre): the row's dot product once more at its slice-order index (k_sell_rows only)
+template <class E, class = void>
+struct EpiHasSliceOut : std::false_type {};
+template <class E>
+struct EpiHasSliceOut<E, std::void_t<typename E::has_slice_out>> : std::true_type {};
 
 // `meta[t]` = {first segment, end segment, first nnz, end nnz} of big tile t (one 16-byte load).
 // The loads of a tile need its extent, and vmcnt retires in order: fetching the extent right
