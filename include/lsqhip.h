@@ -449,6 +449,11 @@ int lsq_model_tanh_create(lsq_ctx *ctx, lsq_mat *J, const double *h_Avalues, con
 int lsq_model_destroy(lsq_model *md);
 lsq_f_callback lsq_model_f(void);
 lsq_g_callback lsq_model_g(void);
+/* what the solves on this model ran on.  sliced_rows / sliced_cols: 1 if J's sliced row / column layout is built.  lsmr_path:
+ * lsq_solver_lsmr_path of the solver that the context's latest lsq_optimize on J kept (0: none, or the context has since
+ * solved on another handle).  pair_tails: how often LM's tail took the predicted and the trial residual in one pass over A
+ * (k_sell_rows_pair) since the model was created.  Read-only; the tests use it to know which kernels a model solve ran. */
+int lsq_model_paths(const lsq_model *md, int *sliced_rows, int *sliced_cols, int *lsmr_path, long long *pair_tails);
 
 /* ---- deterministic synthetic inputs (host side; counter-based RNG) ---- */
 /* CSC with exactly `per_col` distinct sorted rows per column, values N(0,1)/sqrt(per_col). */

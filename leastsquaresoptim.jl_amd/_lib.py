@@ -178,6 +178,7 @@ def lib():
         "lsq_model_destroy": (i, [vp]),
         "lsq_model_f": (F_CALLBACK, []),
         "lsq_model_g": (G_CALLBACK, []),
+        "lsq_model_paths": (i, [vp, c_ip, c_ip, c_ip, C.POINTER(C.c_longlong)]),
         "lsq_synth_sparse": (i, [i, i, i, C.c_ulonglong, c_ip, c_ip, c_dp]),
         "lsq_synth_dense": (i, [i, i, C.c_ulonglong, c_dp]),
         "lsq_synth_uniform": (i, [i, C.c_ulonglong, d, d, c_dp]),

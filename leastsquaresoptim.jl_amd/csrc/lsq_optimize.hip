@@ -1355,6 +1355,7 @@ struct lsq_model {
     double *d_b_perm = nullptr;
     double *d_perm[2] = {nullptr, nullptr};
     const double *perm_of[2] = {nullptr, nullptr};
+    long long pair_tails = 0;  // launches of k_sell_rows_pair (lsq_model_paths)
 };
 static void model_perm_invalidate(lsq_model *md, const double *vec) {   // vec == nullptr: all
     for (int k = 0; k < 2; ++k)
@@ -1679,6 +1680,7 @@ static int model_pair_tail(void *user, lsq_mat *J, const double *dx, const doubl
     LSQ_LAUNCH(k_sell_rows_pair<0>, dim3(grid), dim3(LSQ_BIG_NT), lds, c->stream, sell_dev(S), S.wrows, J->m, dx, J->d_colscale,
                (const double *)md->d_t, J->n, nxpad, e);
     *done = true;
+    ++md->pair_tails;
     if (hipGetLastError() != hipSuccess) return 1;
     if (spec) {
         const int st = lsq_sparse_grad_colsum_spec(J, ftrial, sg->grad, md->d_sspec, sg->gate);
@@ -1818,6 +1820,20 @@ extern "C" int lsq_model_tanh_create(lsq_ctx *c, lsq_mat *J, const double *hA, c
         LSQ_HIP(hipStreamSynchronize(c->stream));
     }
     *out = md;
+    return LSQ_OK;
+}
+
+extern "C" int lsq_model_paths(const lsq_model *md, int *sliced_rows, int *sliced_cols, int *lsmr_path, long long *pair_tails) {
+    if (!md || !sliced_rows || !sliced_cols || !lsmr_path || !pair_tails) {
+        lsq_set_error("lsq_model_paths: null argument");
+        return LSQ_EARG;
+    }
+    const lsq_mat *J = md->J;
+    *sliced_rows = J->kind == LSQ_MAT_CSC && J->srows.active;
+    *sliced_cols = J->kind == LSQ_MAT_CSC && J->scols.active;
+    const LsqWorkspace *w = (const LsqWorkspace *)md->ctx->workspace;
+    *lsmr_path = w && w->J == J && w->solver ? w->solver->last_lsmr_path : 0;
+    *pair_tails = md->pair_tails;
     return LSQ_OK;
 }
 

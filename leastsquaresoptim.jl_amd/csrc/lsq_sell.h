@@ -162,11 +162,177 @@ __device__ __forceinline__ void sell_lane_sum(const double *__restrict__ vp, con
     sell_lane_sum_from<SQ>(vp, ip, 0, L, len, xl, sum, sq, lane);
 }
 
+// ---- the head of a streaming launch --------------------------------------------------------------------------------------
+// The gather vector goes global -> LDS by LDS-DMA (gfx950: global_load_lds_dwordx4, no register destination), so a thread
+// holds no staging array and the FIRST slice of every wave can have its value / index batch requested while the vector is
+// still on its way: one wait (vmcnt(0) in front of the barrier) retires both.  With the vector staged through registers the
+// same prefetch spilled (12-16 doubles of staging + 40 registers of batch per lane at the 128-register cap of a 1024-thread
+// workgroup).
+// The LDS image is lane-linear: 16-byte chunk q * 1024 + tid lands at lds + 2 * (q * 1024 + tid) -- the DMA's destination is
+// "wave-uniform base + lane * 16", the base taken from the first active lane, and the active lanes of a wave are a prefix.
+// `src` must be 16-byte aligned (sell_stage_dma_ok: workgroup-uniform; otherwise the caller stages through registers), `lds`
+// too.  An odd count leaves its last double to a plain load of thread 0, written by sell_stage_tail_write in front of the
+// barrier.  A wave must not END with a DMA outstanding (its LDS may belong to the next workgroup by the time the data lands):
+// every early return behind a sell_stage_dma goes through sell_stage_wait.
+// Every chunk sits behind a per-lane predicate, i.e. in a block of its own that a wave may skip.  A load whose result the compiler
+// still counts as unused on SOME path into these blocks (the register-staging alternative beside them, say) makes it wait
+// vmcnt(0) in front of every chunk, which at run time drains the chunk before it: the alternative path ends in sell_stage_wait
+// for that reason.  What a kernel requests BEFORE the DMA and uses behind it (the first slice's descriptor) is waited for by
+// count and leaves the DMA in flight.
+struct SellStageTail {
+    double v;
+    int at;       // LDS index of the unpaired last element, or -1
+};
+__device__ __forceinline__ bool sell_stage_dma_ok(const double *src) { return ((unsigned long long)src & 15ull) == 0ull; }
+// s_waitcnt vmcnt(0) as the builtin (gfx9 encoding: expcnt and lgkmcnt left at their maxima), which the compiler's own counter
+// bookkeeping sees -- an inline-asm wait it does not
+__device__ __forceinline__ void sell_stage_wait() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+template <int NQ>      // chunks per thread: NQ * 1024 * 2 >= count
+__device__ __forceinline__ SellStageTail sell_stage_dma(const double *__restrict__ src, double *lds, int count, int tid) {
+    typedef const __attribute__((address_space(1))) void *gptr_t;
+    typedef __attribute__((address_space(3))) void *lptr_t;
+    const int nch = count >> 1;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const int ch = q * LSQ_BIG_NT + tid;
+        if (ch < nch) __builtin_amdgcn_global_load_lds((gptr_t)(src + 2 * ch), (lptr_t)(lds + 2 * ch), 16, 0, 0);
+    }
+    SellStageTail t;
+    t.v = 0.0;
+    t.at = -1;
+    if ((count & 1) && tid == 0) {
+        t.v = src[count - 1];
+        t.at = count - 1;
+    }
+    return t;
+}
+__device__ __forceinline__ void sell_stage_tail_write(const SellStageTail &t, double *lds) {
+    if (t.at >= 0) lds[t.at] = t.v;
+}
+
+// The first batch of a slice, requested ahead of the barrier that hands the gather vector over (sell_head_load) and added
+// behind it (sell_lane_sum_head): the same operands, the same additions in the same order as sell_lane_sum -- the first batch
+// is loaded and selected with the clamped forms, which are the identity where the slice has 8 pairs or more.
+// (Named members, not arrays: the head lives across the barrier and several branches, and an array member there kept the
+//  whole struct in scratch memory; the batch itself is a local SellBatch on either side, as everywhere.)
+struct SellHead {
+    double2 a0, a1, a2, a3, a4, a5, a6, a7;
+    unsigned c0, c1, c2, c3, c4, c5, c6, c7;
+    double ta;
+    unsigned tc;
+};
+template <int U>
+__device__ __forceinline__ void sell_head_put(SellHead &H, const SellBatch<U> &B) {
+    static_assert(U == 2 || U == 4 || U == 8, "head batch");
+    H.a0 = B.a[0]; H.c0 = B.c[0];
+    H.a1 = B.a[1]; H.c1 = B.c[1];
+    if constexpr (U >= 4) {
+        H.a2 = B.a[2]; H.c2 = B.c[2];
+        H.a3 = B.a[3]; H.c3 = B.c[3];
+    }
+    if constexpr (U >= 8) {
+        H.a4 = B.a[4]; H.c4 = B.c[4];
+        H.a5 = B.a[5]; H.c5 = B.c[5];
+        H.a6 = B.a[6]; H.c6 = B.c[6];
+        H.a7 = B.a[7]; H.c7 = B.c[7];
+    }
+}
+template <int U>
+__device__ __forceinline__ void sell_head_get(const SellHead &H, SellBatch<U> &B) {
+    B.a[0] = H.a0; B.c[0] = H.c0;
+    B.a[1] = H.a1; B.c[1] = H.c1;
+    if constexpr (U >= 4) {
+        B.a[2] = H.a2; B.c[2] = H.c2;
+        B.a[3] = H.a3; B.c[3] = H.c3;
+    }
+    if constexpr (U >= 8) {
+        B.a[4] = H.a4; B.c[4] = H.c4;
+        B.a[5] = H.a5; B.c[5] = H.c5;
+        B.a[6] = H.a6; B.c[6] = H.c6;
+        B.a[7] = H.a7; B.c[7] = H.c7;
+    }
+}
+// `off` and `L` are SCALARS here (the caller passes them through readfirstlane): every request is "scalar base + the lane's
+// offset", one lane offset for the eight value requests and one for the eight index requests -- with per-lane 64-bit addresses
+// (what sell_batch_load forms from a descriptor in vector registers) the sixteen addresses alone cost 32 registers.
+// ONE form of the request whatever the slice's length (a short slice re-reads its last pair: lines it has requested anyway).
+// Requests of 2, 4 or 8 pairs behind branches, as in sell_lane_sum_from, end in stores to different members of H that the
+// compiler merges into one store through a computed address -- and H then lives in scratch memory.
+__device__ __forceinline__ void sell_head_load(SellHead &H, const double *__restrict__ val, const unsigned short *__restrict__ idx,
+                                               int off, int L, int lane) {
+    typedef const __attribute__((address_space(1))) char *gchar_t;
+    typedef double __attribute__((ext_vector_type(2))) gd2_t;
+    const int np = L >> 1;
+    // (byte offsets of the lane as 32-bit values: the "scalar base + 32-bit lane offset" form of a global load)
+    unsigned vo = 16u * (unsigned)lane, io = 4u * (unsigned)lane;
+    asm volatile("" : "+v"(vo), "+v"(io));      // (formed HERE: hoisted out of this block as 64-bit values they cost an add per request)
+    const char *vb = reinterpret_cast<const char *>(val + off);
+    const char *ib = reinterpret_cast<const char *>(idx + off);
+    H.ta = 0.0;
+    H.tc = 0u;
+    if (L & 1) {
+        unsigned long long vt = (unsigned long long)(vb + (size_t)np * 1024), it = (unsigned long long)(ib + (size_t)np * 256);
+        asm volatile("" : "+s"(vt), "+s"(it));
+        H.ta = *(const __attribute__((address_space(1))) double *)((gchar_t)vt + (vo >> 1));
+        // (the lane's 16-bit index inside an aligned 32-bit word, picked behind the barrier: a 16-bit load is widened where it
+        //  is issued, which is a use -- and a wait -- in front of the barrier)
+        H.tc = *(const __attribute__((address_space(1))) unsigned *)((gchar_t)it + ((io >> 1) & ~3u));
+    }
+    if (np > 0) {
+        SellBatch<8> B;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const size_t q = (size_t)min(u, np - 1);
+            // (scalar bases, pinned: not folded into a per-lane 64-bit address.  The pin goes through an integer, so the pointer
+            //  is rebuilt as a GLOBAL one -- a generic pointer would make these flat loads.)
+            unsigned long long vq = (unsigned long long)(vb + q * 1024), iq = (unsigned long long)(ib + q * 256);
+            asm volatile("" : "+s"(vq), "+s"(iq));
+            const gd2_t v = *(const __attribute__((address_space(1))) gd2_t *)((gchar_t)vq + vo);
+            B.a[u].x = v.x;
+            B.a[u].y = v.y;
+            B.c[u] = *(const __attribute__((address_space(1))) unsigned *)((gchar_t)iq + io);
+        }
+        sell_head_put<8>(H, B);
+    }
+}
+template <int U, bool SQ>
+__device__ __forceinline__ void sell_head_sum_n(const SellHead &H, int np, int len, const double *xl, double &sum, double &sq) {
+    SellBatch<U> B;
+    sell_head_get<U>(H, B);
+    sell_batch_sum<U, true, SQ>(B, 0, np, len, xl, sum, sq);
+}
+template <bool SQ>
+__device__ __forceinline__ void sell_lane_sum_head(const SellHead &H, const double *__restrict__ vp, const unsigned short *__restrict__ ip,
+                                                   int L, int len, const double *xl, double &sum, double &sq, int lane) {
+    const int np = L >> 1;
+    if (np > 4) sell_head_sum_n<8, SQ>(H, np, len, xl, sum, sq);
+    else if (np > 2) sell_head_sum_n<4, SQ>(H, np, len, xl, sum, sq);
+    else if (np > 0) sell_head_sum_n<2, SQ>(H, np, len, xl, sum, sq);
+    if (np > 8) sell_lane_sum_from<SQ, false>(vp, ip, 8, L, len, xl, sum, sq, lane);
+    if (L & 1) {
+        SellTail t;
+        t.a = H.ta;
+        t.c = (unsigned short)(H.tc >> (16 * (lane & 1)));
+        sell_tail_sum<SQ>(t, L, len, xl, sum, sq);
+    }
+}
+
 // The slices of one wave (s0 + wave, + 16, ...), with the next slice's descriptor requested before the current slice's stream.
 //   `out(pos, sum, sq)` stores a lane's result.
-// Contains the workgroup barrier that separates staging the gather vector from the first gather: the first descriptor is
-// requested before it.  (Requesting TWO slices per wave up front made the J*v launch slower, 29.5 us against 23.7 us: the
+// Contains the workgroup barrier that separates staging the gather vector from the first gather: the first slice's descriptor
+// AND its first batch are requested before it (the value addresses need only the slice's wave-uniform {offset, L}; the per-lane
+// word `info` is first used in the sums, behind the barrier -- with a DMA in flight the compiler waits for everything at the
+// first use of a vector load's result).  `before_barrier()` runs between those requests and the barrier (the staged vector's
+// odd tail, the wait for the DMA).  `stop` (workgroup-uniform) ends the launch behind the barrier: the `done` flag of a launch
+// queued behind a finished solve is requested with everything else at the head -- one latency, not two in a row -- and acted
+// on here, where nothing is outstanding any more; the function then returns true and the caller returns.
+// `first` (if have_first): the descriptor of slice s0 + wave, requested by the caller AHEAD of the DMA -- a vector load requested behind
+// it could only be waited for together with it.
+// (Requesting TWO slices per wave up front made the J*v launch slower, 29.5 us against 23.7 us: the
 // stream is not short of requests in flight, a CU's miss queue is already full with 16 waves x 5-8 KB.)
+struct SellNoBeforeBarrier {
+    __device__ __forceinline__ void operator()() const {}
+};
 struct SellSliceRef {
     int2 sm;        // {entry offset, padded entry count}
     unsigned inf;   // position | true count << 13
@@ -187,13 +353,50 @@ struct SellNoSliceHook {
     __device__ __forceinline__ double pre(size_t) const { return 0.0; }
     __device__ __forceinline__ void post(size_t, double, double) const {}
 };
-template <bool SQ, class Out, class Hook = SellNoSliceHook>
-__device__ __forceinline__ void sell_wave_slices(const SellDev &S, int s0, int s1, int wv, int lane, const double *xl, Out out,
-                                                 Hook hook = Hook()) {
+template <bool SQ, class Out, class Hook = SellNoSliceHook, class Before = SellNoBeforeBarrier>
+__device__ __forceinline__ bool sell_wave_slices(const SellDev &S, int s0, int s1, int wv, int lane, const double *xl, Out out,
+                                                 Hook hook = Hook(), Before before_barrier = Before(), int stop = 0,
+                                                 bool have_first = false, SellSliceRef first = SellSliceRef()) {
     constexpr int NW = LSQ_BIG_NT / 64;
     int s = s0 + wv;
-    SellSliceRef A = sell_slice_ref(S, s, s1, lane);
+    SellSliceRef A;
+    A.sm = make_int2(0, 0);
+    A.inf = LSQ_SELL_POS_MASK;
+    if (!have_first) A = sell_slice_ref(S, s, s1, lane);
+    SellHead H;
+    double hp0 = 0.0;
+    // the first slice's {offset, L} as SCALARS: its eight value and eight index requests then share one lane offset
+    // (`info` of a caller's descriptor is not touched before the barrier: merging it here would be a use)
+    const int2 smv = have_first ? first.sm : A.sm;
+    const int2 sm0 = make_int2(__builtin_amdgcn_readfirstlane(smv.x), __builtin_amdgcn_readfirstlane(smv.y));
+    if (s < s1) {                                           // (wave-uniform)
+        sell_head_load(H, S.val, S.idx16, sm0.x, sm0.y, lane);
+        hp0 = hook.pre((size_t)s * 64 + lane);
+    }
+    before_barrier();
     __syncthreads();
+    // (workgroup-uniform: the caller's `done` flag, see there.  The empty asm pins the flag's first USE here: the compiler otherwise
+    //  turns it into a branch condition where it was loaded, and waits for it -- and with it for the DMA -- at the head.)
+    asm volatile("" : "+v"(stop));
+    if (stop) return true;
+    if (s < s1) {                                           // the first slice: its first batch is already here
+        SellSliceRef a;
+        a.sm = sm0;
+        unsigned inf1 = first.inf;
+        asm volatile("" : "+v"(inf1));      // (its first use is HERE, behind the barrier: the compiler otherwise copies it where `first` is chosen)
+        a.inf = have_first ? inf1 : A.inf;
+        A = sell_slice_ref(S, s + NW, s1, lane);
+        const size_t oa = (size_t)a.sm.x + lane * 2;
+        const unsigned pos = a.inf & LSQ_SELL_POS_MASK;
+        const size_t pidx = (size_t)s * 64 + lane;
+        double sum = 0.0, sq = 0.0;
+        sell_lane_sum_head<SQ>(H, S.val + oa, S.idx16 + oa, a.sm.y, (int)(a.inf >> LSQ_SELL_POS_BITS), xl, sum, sq, lane);
+        if (pos != LSQ_SELL_POS_MASK) {
+            out(pos, sum, sq);
+            hook.post(pidx, sum, hp0);
+        }
+        s += NW;
+    }
     for (; s < s1; s += NW) {
         const SellSliceRef a = A;
         A = sell_slice_ref(S, s + NW, s1, lane);
@@ -208,6 +411,7 @@ __device__ __forceinline__ void sell_wave_slices(const SellDev &S, int s0, int s
             hook.post(pidx, sum, hp);
         }
     }
+    return false;
 }
 // an epilogue that wants its rows in slice order as well (has_slice_out): slice_pre / slice_post, see sell_wave_slices
 template <class Epi>
@@ -231,24 +435,47 @@ __global__ void __launch_bounds__(LSQ_BIG_NT) k_sell_rows(SellDev S, int wrows, 
     // the gather vector is fetched FIRST, together with the `done` flag of a finished solve and the epilogue's scalars:
     // one memory latency at the head of the kernel instead of three in a row
     constexpr int XR = (LSQ_LDS_X_MAX + LSQ_BIG_NT - 1) / LSQ_BIG_NT;
-    double xr[XR];
+    SellStageTail xtail;
+    xtail.v = 0.0;
+    xtail.at = -1;
+    const bool dma = !xscale && sell_stage_dma_ok(x);      // (workgroup-uniform)
+    // (the first slice's descriptor: requested ahead of the DMA, see sell_wave_slices)
+    const SellSliceRef ref0 = sell_slice_ref(S, (int)blockIdx.x * S.spw + wv, (int)blockIdx.x < S.nblocks ? ((int)blockIdx.x + 1) * S.spw : 0, lane);
+    int dflag;
+    if (dma) {
+        // an unscaled vector goes straight to LDS; the first slice's batch follows it inside sell_wave_slices, one wait for both
+        xtail = sell_stage_dma<(XR + 1) / 2>(x, xl, nx, tid);
+        dflag = epi.done ? *epi.done : 0;
+        if constexpr (EpiHasBlockPrepare<Epi>::value) epi.block_prepare();
+        if constexpr (EpiHasPrepare<Epi>::value) epi.prepare();
+    } else {
+        double xr[XR];
 #pragma unroll
-    for (int q = 0; q < XR; ++q) xr[q] = x[min(tid + q * LSQ_BIG_NT, nx - 1)];
-    if (xscale) {   // (wave-uniform; the factors travel with the gather vector: still one latency at the head)
-        double sr[XR];
+        for (int q = 0; q < XR; ++q) xr[q] = x[min(tid + q * LSQ_BIG_NT, nx - 1)];
+        if (xscale) {   // (wave-uniform; the factors travel with the gather vector: still one latency at the head)
+            double sr[XR];
 #pragma unroll
-        for (int q = 0; q < XR; ++q) sr[q] = xscale[min(tid + q * LSQ_BIG_NT, nx - 1)];
+            for (int q = 0; q < XR; ++q) sr[q] = xscale[min(tid + q * LSQ_BIG_NT, nx - 1)];
 #pragma unroll
-        for (int q = 0; q < XR; ++q) xr[q] *= sr[q];
-    }
-    const int dflag = epi.done ? *epi.done : 0;
+            for (int q = 0; q < XR; ++q) xr[q] *= sr[q];
+        }
+        dflag = epi.done ? *epi.done : 0;
 
-    if constexpr (EpiHasBlockPrepare<Epi>::value) epi.block_prepare();
-    if constexpr (EpiHasPrepare<Epi>::value) epi.prepare();
+        if constexpr (EpiHasBlockPrepare<Epi>::value) epi.block_prepare();
+        if constexpr (EpiHasPrepare<Epi>::value) epi.prepare();
 #pragma unroll
-    for (int q = 0; q < XR; ++q)
-        if (tid + q * LSQ_BIG_NT < nx) xl[tid + q * LSQ_BIG_NT] = xr[q];
-    if (dflag) return;   // launches queued behind a finished solve stop here
+        for (int q = 0; q < XR; ++q)
+            if (tid + q * LSQ_BIG_NT < nx) xl[tid + q * LSQ_BIG_NT] = xr[q];
+        sell_stage_wait();      // (nothing left that counts as pending: see sell_stage_dma)
+    }
+    // launches queued behind a finished solve stop behind the first barrier (sell_wave_slices: `stop`); without a block, here
+    if ((int)blockIdx.x >= S.nblocks) {
+        sell_stage_wait();
+        int d = dflag;
+        asm volatile("" : "+v"(d));      // (the flag's use stays inside this branch)
+        if (d) return;
+    }
+    bool pending = dma;      // a DMA is outstanding: waited for in front of the first barrier
     constexpr int Q = LSQ_SELL_ROWS_MAX / LSQ_BIG_NT;
     double racc = 0.0;
     for (int w = blockIdx.x; w < S.nblocks; w += gridDim.x) {
@@ -260,11 +487,20 @@ __global__ void __launch_bounds__(LSQ_BIG_NT) k_sell_rows(SellDev S, int wrows, 
             for (int q = 0; q < Q; ++q) pre[q] = epi.pre(base + min(tid + q * LSQ_BIG_NT, rows - 1));
         }
         // (the barrier inside: x staged / the previous window's epilogue is done with yw)
+        auto staged = [&]() {      // (the odd last element of a DMA-staged x; nothing of the DMA is outstanding at the barrier)
+            sell_stage_tail_write(xtail, xl);
+            if (pending) sell_stage_wait();
+        };
+        bool stopped;
         if constexpr (EpiHasSliceOut<Epi>::value)
-            sell_wave_slices<false>(S, s0, s1, wv, lane, xl, [&](unsigned pos, double sum, double) { yw[pos] = sum; },
-                                    SellEpiSliceHook<Epi>{epi});
+            stopped = sell_wave_slices<false>(S, s0, s1, wv, lane, xl, [&](unsigned pos, double sum, double) { yw[pos] = sum; },
+                                              SellEpiSliceHook<Epi>{epi}, staged, dflag, w == (int)blockIdx.x, ref0);
         else
-            sell_wave_slices<false>(S, s0, s1, wv, lane, xl, [&](unsigned pos, double sum, double) { yw[pos] = sum; });
+            stopped = sell_wave_slices<false>(S, s0, s1, wv, lane, xl, [&](unsigned pos, double sum, double) { yw[pos] = sum; },
+                                              SellNoSliceHook(), staged, dflag, w == (int)blockIdx.x, ref0);
+        if (stopped) return;
+        xtail.at = -1;
+        pending = false;
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
@@ -274,6 +510,10 @@ __global__ void __launch_bounds__(LSQ_BIG_NT) k_sell_rows(SellDev S, int wrows, 
                 else epi.seg(base + i, yw[i], racc);
             }
         }
+        // (nothing of this block counts as pending at the loop's head: the compiler merges what is pending there with what is
+        //  pending at the launch's head, and would wait for the DMA before the first request.  The barriers behind the loop wait
+        //  for these stores anyway.)
+        sell_stage_wait();
     }
     // side work (e.g. damped rows) is laid out for LSQ_NT-thread blocks
     for (int e = blockIdx.x; e < epi.extra_blocks; e += gridDim.x)
@@ -630,15 +870,32 @@ __global__ void __launch_bounds__(LSQ_NT) k_sell_vmul(int n, const double *__res
 // ---- J'*y: per (gather window, column) partial sums; k_combine adds the windows ----------------
 // block b = gw * ncb + cb; part layout [gw][n] (SQ: [gw][2n] = dots | squares)
 // window of y -> LDS, all loads of a thread issued before the first use
-__device__ __forceinline__ void sell_cols_stage_y(int b, int ncb, int grows, int m, const double *__restrict__ y, double *yl, int tid) {
+__device__ __forceinline__ SellStageTail sell_cols_stage_y(int b, int ncb, int grows, int m, const double *__restrict__ y, double *yl,
+                                                          int tid) {
     constexpr int YR = LSQ_SELL_GROWS_MAX / LSQ_BIG_NT;
     const int gw = b / ncb, gbase = gw * grows, rows = min(grows, m - gbase);
+    SellStageTail t;
+    t.v = 0.0;
+    t.at = -1;
+    if (sell_stage_dma_ok(y + gbase)) {        // (workgroup-uniform; window bases are multiples of 64 rows)
+        // the zero fill past `rows` (the last window only) BEFORE the DMA is issued: plain LDS writes, nothing to wait for
+        if (rows < grows) {
+#pragma unroll
+            for (int j = 0; j < YR; ++j) {
+                const int i = tid + j * LSQ_BIG_NT;
+                if (i >= rows && i < grows) yl[i] = 0.0;
+            }
+        }
+        return sell_stage_dma<YR / 2>(y + gbase, yl, rows, tid);
+    }
     double yr[YR];
 #pragma unroll
     for (int j = 0; j < YR; ++j) yr[j] = y[gbase + min(tid + j * LSQ_BIG_NT, rows - 1)];
 #pragma unroll
     for (int j = 0; j < YR; ++j)
         if (tid + j * LSQ_BIG_NT < grows) yl[tid + j * LSQ_BIG_NT] = (tid + j * LSQ_BIG_NT < rows) ? yr[j] : 0.0;
+    sell_stage_wait();      // (nothing left that counts as pending: see sell_stage_dma)
+    return t;
 }
 // the workgroup's blocks: a CONTIGUOUS run of block indices (blocks of one gather window are consecutive, so a workgroup that
 // holds several blocks -- wide n: 1280 blocks at n = 50000 -- re-stages its 128 KB window of y only when the window changes,
@@ -653,7 +910,8 @@ __device__ __forceinline__ int sell_cols_first(int nblocks) {
 }
 template <bool SQ>
 __device__ __forceinline__ void sell_cols_pass(const SellDev &S, int ncb, int ccols, int grows, int m, int n,
-                                               const double *__restrict__ y, double *__restrict__ part, double *smem) {
+                                               const double *__restrict__ y, double *__restrict__ part, double *smem,
+                                               SellStageTail ytail, int dflag, const SellSliceRef &ref0) {
     double *yl = smem;                          // LSQ_SELL_GROWS_MAX doubles
     double *ow = smem + LSQ_SELL_GROWS_MAX;     // LSQ_SELL_CCOLS_MAX doubles
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -664,18 +922,24 @@ __device__ __forceinline__ void sell_cols_pass(const SellDev &S, int ncb, int cc
         const int cbase = cb * ccols, cols = min(ccols, n - cbase);
         if (b != b0) {
             __syncthreads();   // the previous block's output pass is done with ow (and its gathers with yl)
-            if (gw != (b - 1) / ncb) sell_cols_stage_y(b, ncb, grows, m, y, yl, tid);
+            if (gw != (b - 1) / ncb) ytail = sell_cols_stage_y(b, ncb, grows, m, y, yl, tid);
         }
         const int s0 = b * S.spw, s1 = s0 + S.spw;
         double *dst = part + (size_t)gw * (SQ ? 2 : 1) * n + cbase;
-        sell_wave_slices<SQ>(S, s0, s1, wv, lane, yl, [&](unsigned pos, double sum, double sq) {   // (lane = one column)
+        const bool stopped = sell_wave_slices<SQ>(S, s0, s1, wv, lane, yl, [&](unsigned pos, double sum, double sq) {   // (lane = one column)
             ow[pos] = sum;
             // (the squares -- the gradient + colsumabs2 pass of multiplied-out matrices, once per g! -- go straight to
             //  memory: a second LDS staging buffer would not fit next to the 128 KiB window)
             if constexpr (SQ) dst[n + pos] = sq;
-        });
+        }, SellNoSliceHook(), [&]() {
+            sell_stage_tail_write(ytail, yl);
+            sell_stage_wait();      // (nothing of a DMA is outstanding at the barrier; the first batch is waited for with it)
+        }, dflag, b == b0, ref0);
+        if (stopped) return;        // (a launch queued behind a finished solve: behind the first barrier)
+        ytail.at = -1;
         __syncthreads();
         for (int i = tid; i < cols; i += LSQ_BIG_NT) dst[i] = ow[i];
+        sell_stage_wait();      // (nothing of this block counts as pending at the loop's head: see k_sell_rows)
     }
 }
 
@@ -684,9 +948,21 @@ __global__ void __launch_bounds__(LSQ_BIG_NT) k_sell_cols(SellDev S, int ncb, in
                                                           const double *__restrict__ y, double *__restrict__ part,
                                                           const int *done) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    // the first window is fetched together with the `done` flag of a finished solve (one latency, not two in a row)
+    // the first window and the first slice's batch are requested together with the `done` flag of a finished solve (one latency,
+    // not two in a row); the flag is acted on behind the first barrier, where no DMA is outstanding
     const int dflag = done ? *done : 0;
-    if (sell_cols_first(S.nblocks) < S.nblocks) sell_cols_stage_y(sell_cols_first(S.nblocks), ncb, grows, m, y, smem, threadIdx.x);
-    if (dflag) return;
-    sell_cols_pass<SQ>(S, ncb, ccols, grows, m, n, y, part, smem);
+    const int bf = sell_cols_first(S.nblocks);
+    // (the first slice's descriptor: requested ahead of the DMA, see sell_wave_slices)
+    const SellSliceRef ref0 = sell_slice_ref(S, bf * S.spw + (int)(threadIdx.x >> 6), bf < S.nblocks ? (bf + 1) * S.spw : 0, threadIdx.x & 63);
+    SellStageTail ytail;
+    ytail.v = 0.0;
+    ytail.at = -1;
+    if (sell_cols_first(S.nblocks) < S.nblocks)
+        ytail = sell_cols_stage_y(sell_cols_first(S.nblocks), ncb, grows, m, y, smem, threadIdx.x);
+    if (bf >= S.nblocks) {      // (no block, nothing staged; otherwise the flag is acted on behind the first barrier)
+        int d = dflag;
+        asm volatile("" : "+v"(d));
+        if (d) return;
+    }
+    sell_cols_pass<SQ>(S, ncb, ccols, grows, m, n, y, part, smem, ytail, dflag, ref0);
 }

@@ -201,6 +201,14 @@ class TanhProblem:
         r.minimizer = self.x.get() if fetch_x else None
         return r
 
+    def paths(self):
+        """What the solves on this problem ran on (lsq_model_paths): sliced layouts built, LSMR driver of the latest solve,
+        launches of LM's one-pass tail so far."""
+        rows, cols, lpath, pairs = C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
+        check(lib().lsq_model_paths(self.model, C.byref(rows), C.byref(cols), C.byref(lpath), C.byref(pairs)))
+        return dict(sliced_rows=bool(rows.value), sliced_cols=bool(cols.value), pair_tails=pairs.value,
+                    lsmr_path={0: None, 1: "reference-order", 2: "four-launch", 3: "three-launch", 4: "general"}[lpath.value])
+
     def close(self):
         L = lib()
         if self.model:
