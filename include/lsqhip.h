@@ -302,13 +302,37 @@ int lsq_solver_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double *
  * J'J = U'U is the unpivoted factorisation of the damped solve with no damping added.  A pivot that is not positive:
  * LSQ_ENOTPD, the 1-based column at which the unpivoted dpotrf of J'J stops in the message -- the one lsq_ldiv_damped sets --
  * and in h_info[0] when h_info is given (0 on success); d_cov / d_stderr are then unspecified, and the solver remains usable
- * for solves and for further covariances.  (A pseudo-inverse for rank-deficient J is not offered, nor a covariance from the
- * QR() factor, which would not square the condition number.)
+ * for solves and for further covariances.  (A pseudo-inverse for rank-deficient J is not offered.  The covariance from
+ * the QR() factor, which does not square the condition number, is lsq_dense_qr_covariance below.)
  * The result has the same bits on every run, under lsq_debug_set(serial = 1), and for either for_lm.  lsq_solver_chol_path
  * afterwards reports the factorisation that was used: 2 or 4 (1 for the few operands that lsq_ldiv_damped, too, keeps in one
  * workgroup: n < 32 with m * n < 20000, or n = 1).  Waits for the stream once, in the middle -- for the info word and s^2,
  * which are read back to back; the last two launches are stream-ordered behind that. */
 int lsq_dense_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double *d_cov, double *d_stderr, int *h_info);
+/* The same from the QR() factor (dense_qr.jl:30-88): Cov = s^2 inv(J'J) = s^2 P X X' P' with J P = Q R, X = inv(R).  J'J is
+ * never formed, so the condition number is not squared: the result keeps its digits where lsq_dense_covariance has lost them
+ * (cond(J) towards 1e8) or returns LSQ_ENOTPD.  `s` is an LSQ_QR solver created on the dense handle J (lsq_dense_create),
+ * either for_lm.  A column-scaled handle means J S.  No damping is involved; J and d_f are not written.
+ * LSQ_EARG, each with a message in lsq_last_error: a solver of another kind; a handle that is not dense; a shape that differs
+ * from the solver's; m < n; d_cov and d_stderr both NULL; d_f with m <= n.
+ *   d_f: NULL (s^2 = 1) or the residual (m doubles, device): s^2 = sum(f.^2) / (m - n) through lsq_sumsq.
+ *   d_cov: NULL or n*n doubles, column-major, in parameter order; both triangles are written with the same bits.
+ *   d_stderr: NULL or n doubles in parameter order, from a kernel of their own with a fixed summation order: the same bits
+ *   with and without d_cov.  They agree with sqrt(diag(cov)) to rounding only.
+ * The factor is whatever lsq_ldiv enqueues for this operand -- the one-workgroup kernel, the multi-CU pivoted Householder, the
+ * two-stage factorisation with CholeskyQR2 or Householder panels, TSQR levels, the full-rank certificate or the pivoted sweep
+ * on R, and the retries after an exchange gives up or a CholeskyQR2 panel breaks down -- run on a solver-owned zero
+ * right-hand side whose solution is discarded; a for_lm solver stacks n zero rows under J (the same R, and the workspace of its
+ * solves stays).  On the certified path X is the inverse the certificate has formed; elsewhere the pivoted triangle is
+ * inverted (the first such call allocates 2 n^2 doubles) and the result is un-permuted on the way out.
+ * The rank is the decision of the solves: xGELSY's at rcond = n eps (lsq_solver_info's qr_rank), or n when the certificate
+ * holds.  h_info[0] (when given) receives it.  rank < n: LSQ_ERANK with a message that states rank and n; d_cov / d_stderr are
+ * then unspecified and the solver stays usable for solves and further covariances.  A pseudo-inverse is not offered.
+ * lsq_solver_qr_path / lsq_solver_qr_panel afterwards report the factorisation that ran.  The result has the same bits on
+ * every run and under lsq_debug_set(serial = 1); for_lm = 0 and for_lm = 1 solvers agree to rounding only (the stacked operand
+ * is split into other slabs).  Waits where the solve waits (the certificate's copy) and once more, for the rank and s^2, which
+ * are read back to back; the last two launches are stream-ordered behind that. */
+int lsq_dense_qr_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double *d_cov, double *d_stderr, int *h_info);
 
 /* The fast paths above that rely on co-resident workgroups (one-launch Cholesky, pipelined triangular solves, the QR panel's slab
  * exchange + pipelined certified solve) wait with a bound; a wait that gives up makes the solve repeat itself on the

@@ -844,6 +844,18 @@ class AllocatedSolver:
         check(lib().lsq_dense_covariance(self.h, J.h, _ptr(df), dcov.ptr, _ptr(dse), info.ctypes.data_as(_lib.c_ip)))
         return DenseCovariance(J.n, dcov.get(), dse.get() if stderr else None)
 
+    def dense_qr_covariance(self, f=None, stderr=True):
+        """lsq_dense_qr_covariance at the values the dense J holds now, from the QR() factor of this solver (J'J is not formed):
+        a DenseCovariance.  `f` as for dense_covariance.  A rank-deficient J raises RankDeficientException."""
+        J = self.J
+        df = f if (f is None or hasattr(f, "ptr")) else DeviceVector(J.ctx, J.m, f)
+        n = J.n if not J.sparse else 0       # (any other handle is refused by the library, with its message)
+        dcov = DeviceVector(J.ctx, n * n)
+        dse = DeviceVector(J.ctx, J.n) if stderr else None
+        info = np.zeros(1, dtype=np.int32)
+        check(lib().lsq_dense_qr_covariance(self.h, J.h, _ptr(df), dcov.ptr, _ptr(dse), info.ctypes.data_as(_lib.c_ip)))
+        return DenseCovariance(J.n, dcov.get(), dse.get() if stderr else None)
+
     def stats(self):
         """lsq_solver_stats: give-ups of the co-residency fast paths and how many solves each stays paused."""
         g, p = (C.c_int * 4)(), (C.c_int * 4)()
@@ -927,6 +939,16 @@ def dense_covariance(Jd, f=None, stderr=True):
     sv = AllocatedSolver(Jd, Cholesky(), for_lm=True)
     try:
         return sv.dense_covariance(f=f, stderr=stderr)
+    finally:
+        sv.free()
+
+
+def dense_qr_covariance(Jd, f=None, stderr=True):
+    """The same from the QR() factor, which does not square the condition number: creates a QR() solver (for_lm=False) on the
+    dense DeviceMatrix, calls AllocatedSolver.dense_qr_covariance and frees the solver."""
+    sv = AllocatedSolver(Jd, QR(), for_lm=False)
+    try:
+        return sv.dense_qr_covariance(f=f, stderr=stderr)
     finally:
         sv.free()
 

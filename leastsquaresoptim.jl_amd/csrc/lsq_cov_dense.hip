@@ -13,6 +13,9 @@
 //   4. k_cov_stderr: s sqrt(sum_{k >= i} X_ik^2), one wavefront per row in a fixed lane-strided order and a fixed butterfly;
 //      a kernel of its own, so that its bits do not depend on whether the covariance was asked for.  It agrees with
 //      sqrt(diag(cov)) to rounding only (the MFMA unit adds the same squares in another order).
+// lsq_dense_qr_covariance (at the end of the file) feeds the same two kernels, or their un-permuting variants, with X = inv(R)
+// of the QR() factor.
+#include <algorithm>
 #include <cmath>
 
 #include "lsq_solver.h"
@@ -27,8 +30,10 @@ typedef double cx_v4d __attribute__((ext_vector_type(4)));
 
 // wave and fragment layout of k_tri_level (lsq_qr.hip): four wavefronts own the 32 x 32 quadrants, 2 x 2 MFMA 16 x 16 x 4 tiles
 // each; operand A: lane & 15 = row, lane >> 4 = k; operand B: lane & 15 = column; accumulator r: row (lane >> 4) + 4 r
+// PERM: accumulator (a, b) of X X' goes to (jp[a], jp[b]) and to its mirror (lsq_dense_qr_covariance on a pivoted factor, J P = Q R)
+template <bool PERM>
 __global__ void __launch_bounds__(256)
-k_cov_xxt(const double *__restrict__ X, int n, double s2, double *__restrict__ C) {
+k_cov_xxt(const double *__restrict__ X, int n, double s2, double *__restrict__ C, const int *__restrict__ jp) {
     __shared__ double sA[CX_T * CX_KS];
     __shared__ double sB[CX_T * CX_KS];
     int t = blockIdx.x, tj = 0;
@@ -97,14 +102,22 @@ k_cov_xxt(const double *__restrict__ X, int n, double s2, double *__restrict__ C
                 const int col = j0 + wc + b * 16 + (lane & 15);
                 if (row < n && col < n && row <= col) {        // (row <= col: always true off the diagonal tiles)
                     const double v = s2 * acc[a][b][r];
-                    C[(size_t)col * n + row] = v;
-                    if (row != col) C[(size_t)row * n + col] = v;
+                    if constexpr (PERM) {
+                        const size_t pr = (size_t)jp[row], pc = (size_t)jp[col];
+                        C[pc * n + pr] = v;
+                        if (row != col) C[pr * n + pc] = v;
+                    } else {
+                        C[(size_t)col * n + row] = v;
+                        if (row != col) C[(size_t)row * n + col] = v;
+                    }
                 }
             }
 }
 
+// PERM: row i of X is parameter jp[i]
+template <bool PERM>
 __global__ void __launch_bounds__(256)
-k_cov_stderr(const double *__restrict__ X, int n, double s, double *__restrict__ se) {
+k_cov_stderr(const double *__restrict__ X, int n, double s, double *__restrict__ se, const int *__restrict__ jp) {
     const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= n) return;
     double acc = 0.0;
@@ -114,7 +127,18 @@ k_cov_stderr(const double *__restrict__ X, int n, double s, double *__restrict__
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
-    if (lane == 0) se[i] = s * sqrt(acc);
+    if (lane == 0) se[PERM ? jp[i] : i] = s * sqrt(acc);
+}
+
+// the n x n upper triangle of a factor that stands in a taller buffer (leading dimension ld > n, reflectors below the
+// diagonal) into a leading-dimension-n image: what lsq_tri_inv_enqueue and k_cov_xxt read.  Below the diagonal U is left alone.
+__global__ void __launch_bounds__(256)
+k_cov_tri_gather(const double *__restrict__ R, int ld, int n, double *__restrict__ U) {
+    const long long tot = (long long)n * n;
+    for (long long e = blockIdx.x * 256LL + threadIdx.x; e < tot; e += (long long)gridDim.x * 256) {
+        const int r = (int)(e % n), cidx = (int)(e / n);
+        if (r <= cidx) U[e] = R[(size_t)cidx * ld + r];
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -185,9 +209,103 @@ extern "C" int lsq_dense_covariance(lsq_solver *s, lsq_mat *J, const double *d_f
     const double s2 = d_f ? ssq / (double)(m - n) : 1.0;
     if (d_cov) {
         const int nt = lsq_div_up(n, CX_T);
-        LSQ_LAUNCH(k_cov_xxt, dim3(nt * (nt + 1) / 2), dim3(256), 0, c->stream, (const double *)s->tri_X, n, s2, d_cov);
+        LSQ_LAUNCH(k_cov_xxt<false>, dim3(nt * (nt + 1) / 2), dim3(256), 0, c->stream, (const double *)s->tri_X, n, s2, d_cov, (const int *)nullptr);
     }
-    if (d_stderr) LSQ_LAUNCH(k_cov_stderr, dim3(lsq_div_up(n, 4)), dim3(256), 0, c->stream, (const double *)s->tri_X, n, sqrt(s2), d_stderr);
+    if (d_stderr) LSQ_LAUNCH(k_cov_stderr<false>, dim3(lsq_div_up(n, 4)), dim3(256), 0, c->stream, (const double *)s->tri_X, n, sqrt(s2), d_stderr,
+                                 (const int *)nullptr);
+    LSQ_HIP(hipGetLastError());
+    return LSQ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// lsq_dense_qr_covariance: the same from the QR() factor, J P = Q R: Cov = s^2 P X X' P', X = inv(R) -- J'J is never formed,
+// so the condition number is not squared.  The factor is the one lsq_qr_solve enqueues for this operand, undamped, with a
+// solver-owned zero right-hand side (a for_lm solver stacks n zero rows: the same R, and the same (M, n) workspace as its
+// solves); its x is discarded.  Where that solve leaves things (lsq_solver::qr_R / qr_ldr / qr_X, pivots in d_tau, the rank in
+// d_info[0]):
+//   certified (qr_path 3): X = Qr2Work::Xinv already, jp = identity: k_cov_xxt / k_cov_stderr as above
+//   pivoted sweep on the stage-1 triangle (2): R in pivoted order, leading dimension n: lsq_tri_inv_enqueue on it
+//   one-stage (1): R at the top of s->d_qr, leading dimension M: k_cov_tri_gather into s->d_T, then lsq_tri_inv_enqueue
+// and on the pivoted ones k_cov_xxt<true> / k_cov_stderr<true> un-permute on the way out.
+// ---------------------------------------------------------------------------------------------
+extern "C" int lsq_dense_qr_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double *d_cov, double *d_stderr,
+                                       int *h_info) {
+    LSQ_RANGE("lsq_dense_qr_covariance");
+    if (!s || !J) { lsq_set_error("lsq_dense_qr_covariance: null argument"); return LSQ_EARG; }
+    if (!d_cov && !d_stderr) {
+        lsq_set_error("lsq_dense_qr_covariance: d_cov and d_stderr are both NULL: nothing to compute");
+        return LSQ_EARG;
+    }
+    if (s->kind != LSQ_QR || !s->d_qr) {
+        lsq_set_error("lsq_dense_qr_covariance: needs a QR() solver created on a dense Jacobian (lsq_dense_create); this "
+                      "solver's kind is %d (a Cholesky() solver has lsq_dense_covariance)", s->kind);
+        return LSQ_EARG;
+    }
+    if (J->kind != LSQ_MAT_DENSE) {
+        lsq_set_error("lsq_dense_qr_covariance: the Jacobian is not a dense handle (lsq_dense_create)");
+        return LSQ_EARG;
+    }
+    if (J->m != s->m || J->n != s->n) {
+        lsq_set_error("lsq_dense_qr_covariance: this solver was allocated for a %d x %d Jacobian, got %d x %d", s->m, s->n, J->m, J->n);
+        return LSQ_EARG;
+    }
+    const int m = J->m, n = J->n;
+    if (m < n) {
+        lsq_set_error("lsq_dense_qr_covariance: inv(J'J) needs m >= n (got m = %d, n = %d)", m, n);
+        return LSQ_EARG;
+    }
+    if (d_f && m <= n) {
+        lsq_set_error("lsq_dense_qr_covariance: the residual variance sum(f.^2) / (m - n) needs m > n (got m = %d, n = %d); "
+                      "pass d_f = NULL for the unscaled inv(J'J)", m, n);
+        return LSQ_EARG;
+    }
+    if (h_info) h_info[0] = 0;
+    if (n <= 0) return LSQ_OK;
+    lsq_ctx *c = s->ctx;
+    LSQ_HIP(hipSetDevice(c->device));
+    // zeros (the right-hand side, m; the damping of a for_lm solver, n <= m) | the solve's x, discarded (n)
+    if (!s->d_cov_buf) {
+        LSQ_HIP(hipMalloc(&s->d_cov_buf, ((size_t)m + n + 8) * sizeof(double)));
+        LSQ_HIP(hipMemsetAsync(s->d_cov_buf, 0, (size_t)m * sizeof(double), c->stream));
+    }
+    const double *zero = s->d_cov_buf;
+    LSQ_TRY(lsq_qr_solve(s, J, zero, s->for_lm ? zero : nullptr, s->d_cov_buf + m, nullptr));
+    const double *X = s->qr_X;
+    const int *jp = nullptr;
+    if (s->last_qr_path != 3 || !X) {
+        const double *U = s->qr_R;
+        if (s->qr_ldr != n) {
+            const long long tot = (long long)n * n;
+            const int g = (int)std::min<long long>((tot + 255) / 256, (long long)c->num_cus * 8);
+            LSQ_LAUNCH(k_cov_tri_gather, dim3(g), dim3(256), 0, c->stream, U, s->qr_ldr, n, s->d_T);
+            U = s->d_T;
+        }
+        LSQ_TRY(lsq_tri_inv_enqueue(s, U, n));
+        X = s->tri_X;
+        jp = (const int *)s->d_tau;
+    }
+    // the one wait beyond the solve's own: the variance and, behind it, the rank decision of the solve
+    double ssq = 0.0;
+    int st4[4] = {0, 0, 0, 0};
+    if (d_f) LSQ_TRY(lsq_sumsq(c, m, d_f, &ssq));
+    LSQ_TRY(lsq_read_ints(c, s->d_info, nullptr, nullptr, nullptr, st4));
+    const int rank = st4[0];
+    s->last_rank = rank;
+    if (h_info) h_info[0] = rank;
+    if (rank < n) {
+        lsq_set_error("RankDeficientException(%d): lsq_dense_qr_covariance: the Jacobian has rank %d < n = %d (xGELSY's decision at "
+                      "rcond = n eps); a pseudo-inverse covariance is not offered", rank, rank, n);
+        return LSQ_ERANK;
+    }
+    const double s2 = d_f ? ssq / (double)(m - n) : 1.0;
+    const int nt = lsq_div_up(n, CX_T);
+    if (jp) {
+        if (d_cov) LSQ_LAUNCH(k_cov_xxt<true>, dim3(nt * (nt + 1) / 2), dim3(256), 0, c->stream, X, n, s2, d_cov, jp);
+        if (d_stderr) LSQ_LAUNCH(k_cov_stderr<true>, dim3(lsq_div_up(n, 4)), dim3(256), 0, c->stream, X, n, sqrt(s2), d_stderr, jp);
+    } else {
+        if (d_cov) LSQ_LAUNCH(k_cov_xxt<false>, dim3(nt * (nt + 1) / 2), dim3(256), 0, c->stream, X, n, s2, d_cov, jp);
+        if (d_stderr) LSQ_LAUNCH(k_cov_stderr<false>, dim3(lsq_div_up(n, 4)), dim3(256), 0, c->stream, X, n, sqrt(s2), d_stderr, jp);
+    }
     LSQ_HIP(hipGetLastError());
     return LSQ_OK;
 }

@@ -1318,6 +1318,7 @@ int lsq_qr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_d
         LSQ_LAUNCH(k_rhs, dim3(lsq_div_up(lu, LSQ_NT)), dim3(LSQ_NT), 0, c->stream, d_y, m, lu, s->d_qu);
         const int mn = std::min(M, n);
         s->last_qr_path = 1;
+        s->qr_R = s->d_qr; s->qr_ldr = M; s->qr_X = nullptr;
         if (lsq_qr2_applies(M, n)) {
             double *R2 = nullptr, *rhs2 = nullptr;
             LSQ_TRY(lsq_qr2_factor(s, M, n, &R2, &rhs2));
@@ -1347,6 +1348,7 @@ int lsq_qr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_d
                 LSQ_HIP(hipGetLastError());
                 s->last_rank = -1;
                 s->last_qr_path = 3;
+                s->qr_R = R2; s->qr_ldr = n; s->qr_X = q->Xinv;
                 s->fb_qrx.solve_done(!q->no_exchange);
                 s->fb_cholqr.solve_done(q->cholqr_used);
                 if (nmul) *nmul = 1;
@@ -1384,6 +1386,7 @@ int lsq_qr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_d
                                        vn1, vn2);
                 }
             }
+            s->qr_R = R2; s->qr_ldr = n;
             int ph = 0;
             if (n <= QRK_MAXN) {
                 if (!have_rank)

@@ -95,6 +95,10 @@ struct lsq_solver {
     size_t work_elems = 0;
     std::vector<double> h_R;   // n*n host copy for pivoting / rank decisions
     int last_rank = -1;
+    // where the last lsq_qr_solve left its factor (lsq_dense_qr_covariance): the triangle R (reflectors may stand below its
+    // diagonal) with its leading dimension, pivots in d_tau; certified path: X = inv(R) as well (Qr2Work::Xinv), else nullptr
+    const double *qr_R = nullptr, *qr_X = nullptr;
+    int qr_ldr = 0;
     int (*precond_cb)(double *, lsq_mat *, const double *, void *) = nullptr;   // LSMR(preconditioner!, P), diagonal P
     void *precond_user = nullptr;
     // LSMR(preconditioner!, P) with ANY P supporting ldiv! (lsq_lsmr_general.hip): update = preconditioner!(P, x, J, damp),

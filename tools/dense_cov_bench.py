@@ -1,7 +1,10 @@
 """lsq_dense_covariance (lsq_cov_dense.hip) against one Cholesky() lsq_ldiv_damped on the same handle and solver, in the same
 run; one JSON line per size.
 
-    python tools/dense_cov_bench.py [--reps 20]
+    python tools/dense_cov_bench.py [--reps 20] [--solver cholesky|qr]
+
+--solver qr: lsq_dense_qr_covariance against one lsq_ldiv of the same QR() solver (for_lm = 0), same sizes, same three calls.
+On the certified path the covariance is that solve's launches plus k_cov_xxt + k_cov_stderr and one more wait.
 
 Sizes: 4096 x 512 (C2) and 16384 x 2048 (the C3 size).  Per size three calls are timed, interleaved (solve, cov + stderr,
 stderr only, solve, ...) so that a neighbour on the machine hits all three alike: HIP events on the library's stream around the
@@ -85,12 +88,47 @@ def bench(ctx, tag, m, n, reps, warmup=3):
         o.free()
 
 
+def bench_qr(ctx, tag, m, n, reps, warmup=3):
+    L = lsq.lib()
+    rng = np.random.default_rng(11)
+    Jd = lsq.DeviceMatrix(ctx, lsq.synthetic.dense_inputs(m, n, 5).reshape((m, n), order="F"))
+    sv = lsq.AllocatedSolver(Jd, lsq.QR(), for_lm=False)
+    dx, dy = lsq.DeviceVector(ctx, n), lsq.DeviceVector(ctx, m, rng.standard_normal(m))
+    dcov, dse = lsq.DeviceVector(ctx, n * n), lsq.DeviceVector(ctx, n)
+    calls = {
+        "solve": lambda: sv.ldiv_(dx, dy),
+        "cov_stderr": lambda: lsq._lib.check(L.lsq_dense_qr_covariance(sv.h, Jd.h, dy.ptr, dcov.ptr, dse.ptr, None)),
+        "stderr_only": lambda: lsq._lib.check(L.lsq_dense_qr_covariance(sv.h, Jd.h, dy.ptr, None, dse.ptr, None)),
+    }
+    evs = HipEvents(ctx)
+    t = {k: [] for k in calls}
+    paths = {}
+    for r in range(warmup + reps):
+        for k, fn in calls.items():
+            sec = evs.timed(ctx, fn)
+            info = sv.info()
+            paths[k] = "%s/%s" % (info["qr_path"], info["qr_panel"])
+            if r >= warmup:
+                t[k].append(sec)
+    out = {"bench": "dense_qr_covariance", "size": tag, "m": m, "n": n, "reps": reps, "qr_path": paths,
+           "flops": {"qr": 2.0 * m * n * n - 2.0 * n ** 3 / 3.0, "inverse": n ** 3 / 3.0, "xxt": n ** 3 / 3.0}}
+    for k in calls:
+        out[k] = {"event_median_s": statistics.median(t[k]), "event_min_s": min(t[k])}
+    out["cov_over_solve"] = out["cov_stderr"]["event_median_s"] / out["solve"]["event_median_s"]
+    out["stderr_over_solve"] = out["stderr_only"]["event_median_s"] / out["solve"]["event_median_s"]
+    out["cov_minus_solve_s"] = out["cov_stderr"]["event_median_s"] - out["solve"]["event_median_s"]
+    print(json.dumps(out), flush=True)
+    for o in (sv, Jd):
+        o.free()
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--solver", choices=["cholesky", "qr"], default="cholesky")
     ap.add_argument("--only", choices=[s[0] for s in SIZES])
     a = ap.parse_args()
     ctx = lsq.default_context()
     for tag, m, n in SIZES:
         if a.only in (None, tag):
-            bench(ctx, tag, m, n, a.reps)
+            (bench_qr if a.solver == "qr" else bench)(ctx, tag, m, n, a.reps)
