@@ -20,13 +20,9 @@
 #include <chrono>
 #include <climits>
 
-#include "lsq_solver.h"
+#include "lsq_loop.h"      // the trust-region constants
 
 namespace {
-
-constexpr double MIN_DELTA = 1e-16, MAX_DELTA = 1e16, MIN_STEP_QUALITY = 1e-3;
-constexpr double MIN_DIAGONAL = 1e-6, MAX_DIAGONAL = 1e32;
-constexpr double DECREASE_THRESHOLD = 0.25, INCREASE_THRESHOLD = 0.75;
 
 struct BtDev {      // per-block state, device arrays of length B
     double *delta, *decf, *ssr, *ssr0, *maxdx, *maxgr, *wn_gn, *wn_gr, *alpha, *wn_dx;

@@ -1,174 +1,12 @@
-// Solver plug point (ldiv!), the Levenberg-Marquardt / Dogleg trust-region loops on device
-// buffers (levenberg_marquardt.jl:39-144, dogleg.jl:41-203: host control flow, device arrays),
-// and the built-in device-side tanh model used by the synthetic benchmarks.
+// The Levenberg-Marquardt / Dogleg trust-region loops on device buffers (levenberg_marquardt.jl:39-144, dogleg.jl:41-203: host
+// control flow, device arrays).  The solver handle they drive is lsq_solver.hip; the built-in tanh model whose passes they fuse
+// into their own is lsq_model.hip, reached through the hooks of lsq_loop.h.
 #include <chrono>
 #include <cmath>
 #include <cstring>
 
-#include "lsq_solver.h"
+#include "lsq_loop.h"
 #include "lsq_spmv.h"
-
-// constants that shape trajectories (types.jl:107-111, dogleg.jl:38-39)
-static constexpr double MIN_DELTA = 1e-16, MAX_DELTA = 1e16, MIN_STEP_QUALITY = 1e-3;
-static constexpr double MIN_DIAGONAL = 1e-6, MAX_DIAGONAL = 1e32;
-static constexpr double DECREASE_THRESHOLD = 0.25, INCREASE_THRESHOLD = 0.75;
-
-// scalar slots used by the loops (ctx->d_slots)
-enum { SL_GRAD = 8, SL_DX = 9, SL_NONFIN = 10, SL_TRIAL = 11, SL_PRED = 12, SL_SSR = 13, SL_W0 = 14, SL_W1 = 15,
-       SL_W2 = 16, SL_SUM = 17 };
-
-// ---------------------------------------------------------------------------------------------
-// solver objects
-// ---------------------------------------------------------------------------------------------
-extern "C" int lsq_solver_create(lsq_ctx *c, lsq_mat *J, int kind, int for_lm, lsq_solver **out) {
-    LSQ_RANGE("lsq_solver_create");
-    if (!c || !J || !out) return LSQ_EARG;
-    if (kind == LSQ_QR && J->kind != LSQ_MAT_DENSE) {
-        lsq_set_error("solver QR() is not available for sparse Jacobians. Choose between Cholesky() and LSMR()");
-        return LSQ_EARG;  // types.jl:115-117
-    }
-    const bool blockdiag = kind == LSQ_CHOLESKY && J->kind == LSQ_MAT_CSC && J->bd_blocks > 0;   // lsq_blockdiag_create
-    const bool bordered = kind == LSQ_CHOLESKY && J->kind == LSQ_MAT_CSC && J->br_blocks > 0;   // lsq_blockdiag_bordered_create
-    if (kind == LSQ_CHOLESKY && J->kind != LSQ_MAT_DENSE && !blockdiag && !bordered) {
-        lsq_set_error("MethodError: no AbstractAllocatedSolver for Cholesky() with a sparse Jacobian "
-                      "(dense_cholesky.jl:19 requires a StridedVecOrMat)");
-        return LSQ_EARG;
-    }
-    LSQ_HIP(hipSetDevice(c->device));
-    lsq_solver *s = new lsq_solver();
-    s->ctx = c;
-    s->kind = kind;
-    s->for_lm = for_lm ? 1 : 0;
-    s->m = J->m;
-    s->n = J->n;
-    int st = (kind == LSQ_LSMR) ? lsq_lsmr_alloc(s) : (kind == LSQ_BLOCK_QR) ? lsq_blockqr_solver_alloc(s, J)
-             : blockdiag ? lsq_blockdiag_solver_alloc(s, J) : bordered ? lsq_bordered_solver_alloc(s, J) : lsq_dense_solver_alloc(s);
-    if (st != LSQ_OK) {
-        delete s;
-        return st;
-    }
-    *out = s;
-    return LSQ_OK;
-}
-
-extern "C" int lsq_solver_destroy(lsq_solver *s) {
-    if (!s) return LSQ_OK;
-    hipStreamSynchronize(s->ctx->stream);
-    if (s->kind == LSQ_LSMR) lsq_lsmr_free(s);
-    else lsq_dense_solver_free(s);     // (also the block-diagonal solvers: all they own is d_info, freed there)
-    hipFree(s->d_cov_info); hipFree(s->d_cov_buf);     // lsq_solver_covariance
-    delete s;
-    return LSQ_OK;
-}
-
-// include/lsqhip.h: "calls that return host scalars synchronise the stream".  The LSMR driver learns about the stop from a
-// progress word that the committing workgroup publishes BEFORE its sibling workgroups have finished writing x (lsq_lsmr3.h:
-// relaxed publish), and launches of the look-ahead may still be queued: the public entry points drain the stream
-// before they hand nmul back, so that x may be read from another stream or with a blocking copy.  (Polled, not
-// hipStreamSynchronize: what is left in the queue is microseconds of work, a sleeping wait wakes up after ~50 us.)  The LM /
-// Dogleg loops call lsq_lsmr_solve directly and stay stream-ordered.
-static int lsmr_drain(lsq_solver *s) {
-    for (;;) {
-        const hipError_t q = hipStreamQuery(s->ctx->stream);
-        if (q == hipSuccess) return LSQ_OK;
-        if (q != hipErrorNotReady) {
-            lsq_set_error("HIP error behind an LSMR solve: %s", hipGetErrorString(q));
-            return LSQ_EHIP;
-        }
-    }
-}
-
-extern "C" int lsq_ldiv(lsq_solver *s, lsq_mat *J, const double *y, double *x, int *nmul) {
-    LSQ_RANGE("lsq_ldiv");
-    if (!s || !J || !y || !x) return LSQ_EARG;
-    if (s->for_lm && s->kind == LSQ_QR) {
-        lsq_set_error("ldiv!: this QR solver was allocated for LevenbergMarquardt (damped)");
-        return LSQ_EDIM;
-    }
-    switch (s->kind) {
-    case LSQ_LSMR: LSQ_TRY(lsq_lsmr_solve(s, J, y, nullptr, x, nmul)); return lsmr_drain(s);
-    case LSQ_CHOLESKY:
-        if (s->br_blocks) return lsq_bordered_solve(s, J, y, nullptr, x, nmul);     // (refused: LM only)
-        return s->bd_blocks ? lsq_blockdiag_solve(s, J, y, nullptr, x, nmul) : lsq_cholesky_solve(s, J, y, nullptr, x, nmul);
-    case LSQ_BLOCK_QR: return lsq_blockqr_solve(s, J, y, nullptr, x, nmul);
-    default: return lsq_qr_solve(s, J, y, nullptr, x, nmul);
-    }
-}
-
-extern "C" int lsq_ldiv_damped(lsq_solver *s, lsq_mat *J, const double *y, double *damp, double *x, int *nmul) {
-    LSQ_RANGE("lsq_ldiv_damped");
-    if (!s || !J || !y || !x || !damp) return LSQ_EARG;
-    switch (s->kind) {
-    case LSQ_LSMR: LSQ_TRY(lsq_lsmr_solve(s, J, y, damp, x, nmul)); return lsmr_drain(s);
-    case LSQ_CHOLESKY:
-        if (s->br_blocks) return lsq_bordered_solve(s, J, y, damp, x, nmul);
-        return s->bd_blocks ? lsq_blockdiag_solve(s, J, y, damp, x, nmul) : lsq_cholesky_solve(s, J, y, damp, x, nmul);
-    case LSQ_BLOCK_QR: return lsq_blockqr_solve(s, J, y, damp, x, nmul);
-    default: return lsq_qr_solve(s, J, y, damp, x, nmul);
-    }
-}
-
-extern "C" int lsq_solver_set_preconditioner(lsq_solver *s, lsq_precond_callback cb, void *user) {
-    if (!s) return LSQ_EARG;
-    if (s->kind != LSQ_LSMR && cb) {
-        lsq_set_error("preconditioners apply to the LSMR solver only (types.jl:82-86)");
-        return LSQ_EARG;
-    }
-    s->precond_cb = cb;
-    s->precond_user = user;
-    return LSQ_OK;
-}
-
-extern "C" int lsq_solver_qr_panel(const lsq_solver *s, int *kind) {
-    if (!s || !kind) { lsq_set_error("lsq_solver_qr_panel: null argument"); return LSQ_EARG; }
-    *kind = s->last_qr_panel;
-    return LSQ_OK;
-}
-extern "C" int lsq_solver_qr_path(const lsq_solver *s, int *path) {
-    if (!s || !path) { lsq_set_error("lsq_solver_qr_path: null argument"); return LSQ_EARG; }
-    *path = s->last_qr_path;
-    return LSQ_OK;
-}
-
-extern "C" int lsq_solver_stats(const lsq_solver *s, int h_giveups[4], int h_paused[4]) {
-    if (!s) { lsq_set_error("lsq_solver_stats: null argument"); return LSQ_EARG; }
-    const LsqFallback *fb[4] = {&s->fb_tiles, &s->fb_pipe, &s->fb_qrx, &s->fb_cholqr};
-    for (int i = 0; i < 4; ++i) {
-        if (h_giveups) h_giveups[i] = fb[i]->giveups;
-        if (h_paused) h_paused[i] = fb[i]->cooldown;
-    }
-    return LSQ_OK;
-}
-
-extern "C" int lsq_solver_chol_path(const lsq_solver *s, int *path) {
-    if (!s || !path) { lsq_set_error("lsq_solver_chol_path: null argument"); return LSQ_EARG; }
-    *path = s->last_chol_path;
-    return LSQ_OK;
-}
-
-extern "C" int lsq_solver_lsmr_path(const lsq_solver *s, int *path) {
-    if (!s || !path) { lsq_set_error("lsq_solver_lsmr_path: null argument"); return LSQ_EARG; }
-    *path = s->last_lsmr_path;
-    return LSQ_OK;
-}
-
-extern "C" int lsq_solver_info(const lsq_solver *s, int *iter, int *istop, int *rank) {
-    if (iter) *iter = s->last_iter;
-    if (istop) *istop = s->last_istop;
-    if (rank) {
-        *rank = -1;
-        if (s->kind == LSQ_QR && s->d_info) {
-            LSQ_HIP(hipStreamSynchronize(s->ctx->stream));
-            LSQ_HIP(hipMemcpy(rank, s->d_info, sizeof(int), hipMemcpyDeviceToHost));
-        } else if (s->kind == LSQ_BLOCK_QR && s->bq_solved) {    // the sum of the block ranks
-            std::vector<int> hr((size_t)s->bd_blocks);
-            LSQ_TRY(lsq_solver_blockdiag_ranks(s, hr.data()));
-            *rank = 0;
-            for (int v : hr) *rank += v;
-        }
-    }
-    return LSQ_OK;
-}
 
 // ---------------------------------------------------------------------------------------------
 // fused outer-loop kernels
@@ -435,13 +273,6 @@ k_lincomb(int n, double a, const double *__restrict__ p, double b, const double 
     }
 }
 
-static inline int ngrid(const lsq_ctx *c, long long n) {
-    long long g = (n + LSQ_NT - 1) / LSQ_NT;
-    long long cap = (long long)c->num_cus * 8;
-    if (g > cap) g = cap;
-    return g < 1 ? 1 : (int)g;
-}
-
 // sum(x^2) -> slot: tree reduction, or the reference's left-to-right order for small problems
 static int sumsq_to_slot(lsq_ctx *c, bool exact, long long n, const double *x, int ctr, double *d_out,
                          LsqSlotPublish pub = LsqSlotPublish()) {
@@ -456,35 +287,10 @@ static int sumsq_to_slot(lsq_ctx *c, bool exact, long long n, const double *x, i
 }
 // f!(out, x) followed by sum(out.^2) -> slot.  When f! is the library's own device-side model on the sliced-row layout the
 // sum rides in the residual kernel's epilogue (no second pass over the m-vector: 8 MB and a launch less per iteration at C4)
-static int model_f(double *out, const double *x, void *user);
-static int model_g(lsq_mat *J, const double *x, void *user);
-// mirror: the caller expects model_pair_tail to read `out` next -- the pass leaves it in slice order too (no k_sell_perm_rows)
-static int model_f_sumsq(void *user, double *out, const double *x, int ctr, double *d_out, LsqSlotPublish pub, bool *done,
-                         const int *skip = nullptr, bool mirror = false);
-// the start point of a solve on the model's sliced rows: tanh(x0), 1 - tanh(x0)^2 and the first non-finite index of x0 (-> slot)
-// in one launch; *done tells whether it applied (else nothing was launched)
-static int model_start_point(void *user, const double *x, double *d_nonfin, bool *done);
-// an error return between model_start_point and the g! that would have consumed its factors: nothing stays recorded
-static void model_forget_point(void *user);
-// predicted residual |J dx - f|^2 AND f!(x_trial) with its sum of squares in ONE pass over the model's matrix
-// (k_sell_rows_pair, lsq_sell.h); *done tells whether it applied (else nothing was launched: the caller takes the two passes)
-// sg (optional): also queue the NEXT iteration's gradient + colsumabs2 pass behind it, guarded by the acceptance and convergence
-// tests the kernel takes on the device (lsq_sparse_grad_colsum_spec); sg->launched tells whether that pass was queued
-struct SpecGrad {
-    int *gate;          // this pass's skip word (non-zero until the pair kernel clears it)
-    double ssr;         // the current sum of squares (what the host will test rho against)
-    double *grad;       // where the gradient goes
-    bool launched;
-    double xtol, ftol, gtol;    // the loop's tolerances (what the host's assess() will test with)
-};
-static int model_pair_tail(void *user, lsq_mat *J, const double *dx, const double *fcur, double *ftrial, const double *xt,
-                           double *slot_pred, double *slot_trial, LsqSlotPublish pub, const int *skip, bool *done,
-                           SpecGrad *sg = nullptr);
-// buffers for tanh(xt) and 1 - tanh(xt)^2 when the model's next f!(., xt) can take them from the step kernel (else nulls)
-static void model_trial_buffers(void *user, const double *xt, double **t_out, double **s_out);
+// (mirror: model_f_sumsq, lsq_loop.h)
 static int f_then_sumsq(lsq_ctx *c, bool exact, lsq_f_callback f, void *user, long long m, double *out, const double *x, int ctr,
                         double *d_out, LsqSlotPublish pub = LsqSlotPublish(), const int *skip = nullptr, bool mirror = false) {
-    if (!exact && f == model_f) {
+    if (!exact && model_is_builtin(f)) {
         bool fused = false;
         if (model_f_sumsq(user, out, x, ctr, d_out, pub, &fused, skip, mirror) != 0) {
             lsq_set_error("user callback reported failure");
@@ -499,11 +305,33 @@ static int f_then_sumsq(lsq_ctx *c, bool exact, lsq_f_callback f, void *user, lo
 }
 // sum((J d - f)^2) -> slot (f may be null: sum((J d)^2))
 static int predicted_to_slot(lsq_ctx *c, bool exact, lsq_mat *J, const double *d, const double *f, double *scratch,
-                             int ctr, double *d_out, LsqSlotPublish pub = LsqSlotPublish(), const int *skip = nullptr);
+                             int ctr, double *d_out, LsqSlotPublish pub = LsqSlotPublish(), const int *skip = nullptr) {
+    if (exact) {
+        LSQ_TRY(lsq_exact_product(J, 0, d, scratch));
+        return lsq_seq_reduce(c, f ? 3 : 1, J->m, scratch, f, nullptr, d_out);
+    }
+    if (f) {
+        EpiPredict ep{skip, 0, f, d_out, c->d_partials, lsq_ctr(c, ctr), pub};
+        return launch_product(J, 0, d, ep);
+    }
+    EpiSumsq es{nullptr, 0, d_out, c->d_partials, lsq_ctr(c, ctr)};
+    return launch_product(J, 0, d, es);
+}
 static int wdot_to_slot(lsq_ctx *c, bool exact, int n, const double *x, const double *y, const double *w, int ctr,
-                        double *d_out);
+                        double *d_out) {
+    if (exact) return lsq_seq_reduce(c, 2, n, x, y, w, d_out);
+    int g = lsq_div_up(n > 0 ? n : 1, LSQ_NT), cap = c->num_cus * 8;
+    LSQ_LAUNCH(k_wdot_slot, dim3(g > cap ? cap : g), dim3(LSQ_NT), 0, c->stream, n, x, y, w, c->d_partials,
+                       lsq_ctr(c, ctr), d_out);
+    return LSQ_OK;
+}
 // g = J'f
-static int gradient_into(lsq_ctx *c, bool exact, lsq_mat *J, const double *f, double *g);
+static int gradient_into(lsq_ctx *c, bool exact, lsq_mat *J, const double *f, double *g) {
+    (void)c;
+    if (exact) return lsq_exact_product(J, 1, f, g);
+    EpiGrad eg{nullptr, 0, g, nullptr, nullptr};
+    return launch_product(J, 1, f, eg);
+}
 
 struct LoopBuffers {
     lsq_ctx *c;
@@ -539,6 +367,10 @@ void lsq_workspace_free(void *p) {
     if (w->solver) lsq_solver_destroy(w->solver);
     delete w;
 }
+int lsq_workspace_lsmr_path(const lsq_ctx *c, const lsq_mat *J) {
+    const LsqWorkspace *w = (const LsqWorkspace *)c->workspace;
+    return w && w->J == J && w->solver ? w->solver->last_lsmr_path : 0;
+}
 
 static int alloc_loop(LoopBuffers &b, lsq_ctx *c, int m, int n, const lsq_options *o, bool dogleg) {
     b.c = c; b.m = m; b.n = n;
@@ -567,34 +399,6 @@ static int alloc_loop(LoopBuffers &b, lsq_ctx *c, int m, int n, const lsq_option
     }
     LSQ_HIP(hipStreamSynchronize(c->stream));
     return LSQ_OK;
-}
-
-static int predicted_to_slot(lsq_ctx *c, bool exact, lsq_mat *J, const double *d, const double *f, double *scratch,
-                             int ctr, double *d_out, LsqSlotPublish pub, const int *skip) {
-    if (exact) {
-        LSQ_TRY(lsq_exact_product(J, 0, d, scratch));
-        return lsq_seq_reduce(c, f ? 3 : 1, J->m, scratch, f, nullptr, d_out);
-    }
-    if (f) {
-        EpiPredict ep{skip, 0, f, d_out, c->d_partials, lsq_ctr(c, ctr), pub};
-        return launch_product(J, 0, d, ep);
-    }
-    EpiSumsq es{nullptr, 0, d_out, c->d_partials, lsq_ctr(c, ctr)};
-    return launch_product(J, 0, d, es);
-}
-static int wdot_to_slot(lsq_ctx *c, bool exact, int n, const double *x, const double *y, const double *w, int ctr,
-                        double *d_out) {
-    if (exact) return lsq_seq_reduce(c, 2, n, x, y, w, d_out);
-    int g = lsq_div_up(n > 0 ? n : 1, LSQ_NT), cap = c->num_cus * 8;
-    LSQ_LAUNCH(k_wdot_slot, dim3(g > cap ? cap : g), dim3(LSQ_NT), 0, c->stream, n, x, y, w, c->d_partials,
-                       lsq_ctr(c, ctr), d_out);
-    return LSQ_OK;
-}
-static int gradient_into(lsq_ctx *c, bool exact, lsq_mat *J, const double *f, double *g) {
-    (void)c;
-    if (exact) return lsq_exact_product(J, 1, f, g);
-    EpiGrad eg{nullptr, 0, g, nullptr, nullptr};
-    return launch_product(J, 1, f, eg);
 }
 
 // utils.jl:7-31: an if/elseif chain -- at most one flag fires
@@ -756,7 +560,7 @@ static int start_residual(lsq_ctx *c, lsq_mat *J, lsq_f_callback f, void *user, 
     }
     static_assert(SL_TRIAL == SL_NONFIN + 1, "the two scalars of the loop head travel together");
     bool head = false;
-    if (f == model_f && model_start_point(user, x, c->d_slots + SL_NONFIN, &head) != 0) return LSQ_EHIP;
+    if (model_is_builtin(f) && model_start_point(user, x, c->d_slots + SL_NONFIN, &head) != 0) return LSQ_EHIP;
     if (!head) LSQ_TRY(lsq_first_nonfinite_to_slot(c, n, x, c->d_slots + SL_NONFIN));
     const LsqSlotPublish pub = lsq_slots_ticket(c, SL_NONFIN, 2);
     double sl[2];
@@ -772,13 +576,146 @@ static int start_residual(lsq_ctx *c, lsq_mat *J, lsq_f_callback f, void *user, 
     return LSQ_OK;
 }
 
-static int optimize_lm_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat *J, double *x_user, double *fcur_user,
-                            lsq_f_callback f, lsq_g_callback g, void *user, const lsq_options *o, lsq_result *r);
-static int optimize_lm(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat *J, double *x_user, double *fcur_user,
-                       lsq_f_callback f, lsq_g_callback g, void *user, const lsq_options *o, lsq_result *r) {
-    ShardedExit ex{c, o};
-    return ex.finish(optimize_lm_loop(c, sv, b, J, x_user, fcur_user, f, g, user, o, r));
+// x_trial = x - dx with max|dx| and the first non-finite index of x_trial -> slots (levenberg_marquardt.jl:106, dogleg.jl:160);
+// model: f! is the built-in model's, which takes tanh(x_trial) from this launch
+static int launch_step(lsq_ctx *c, bool model, void *user, int gn, int n, const double *x, const double *dx, double *xt,
+                       const int *skip = nullptr) {
+    double *t_out = nullptr, *s_out = nullptr;
+    if (model) model_trial_buffers(user, xt, &t_out, &s_out);
+    LSQ_LAUNCH(k_step, dim3(gn), dim3(LSQ_NT), 0, c->stream, n, x, dx, xt, c->d_partials, lsq_ctr(c, 5), c->d_slots + SL_DX,
+               c->d_slots + SL_NONFIN, t_out, s_out, skip);
+    LSQ_HIP(hipGetLastError());
+    return LSQ_OK;
 }
+
+// A rank frozen after convergence keeps taking part in the exchange until every problem has converged (*all)
+static int frozen_turn(const lsq_options *o, double ssr, double maxabs_gr, double *gssr, double *ggr, bool *all) {
+    int a = 1;
+    *gssr = ssr; *ggr = maxabs_gr;
+    LSQ_TRY(global_exchange(o, gssr, ggr, &a));
+    *all = a != 0;
+    return LSQ_OK;
+}
+
+// check_isfinite(x) at the top of iteration `iter` (utils.jl:70-75)
+static int nonfinite_exit(lsq_result *r, int nonfinite_at, int iter) {
+    r->bad_index = nonfinite_at;
+    r->iterations = iter - 1;
+    lsq_set_error("IsFiniteException: non-finite x at index %d", nonfinite_at);
+    return LSQ_ENONFINITE;
+}
+
+// what both loops count and report
+struct LoopTally {
+    int f_calls = 0, g_calls = 0, mul_calls = 0, xc = 0, fc = 0, gc = 0;
+    long long inner_total = 0;
+};
+static int finish_result(lsq_ctx *c, lsq_result *r, int optimizer, double ssr, int iter, bool converged, const LoopTally &t) {
+    LSQ_HIP(hipStreamSynchronize(c->stream));
+    r->optimizer = optimizer;
+    r->ssr = ssr;
+    r->iterations = iter;
+    r->converged = converged; r->x_converged = t.xc; r->f_converged = t.fc; r->g_converged = t.gc;
+    r->f_calls = t.f_calls; r->g_calls = t.g_calls; r->mul_calls = t.mul_calls;
+    r->lsmr_iterations = t.inner_total;
+    return LSQ_OK;
+}
+
+// row-sharded single problem: a sum over residual rows is completed across the ranks by the hook (a device buffer, in place,
+// ordered on the stream)
+static int rows_sum(lsq_ctx *c, const lsq_options *o, double *d_buf, int count) {
+    if (o->row_allreduce(d_buf, count, (void *)c->stream, o->row_allreduce_user) != 0) {
+        lsq_set_error("row all-reduce callback reported failure");
+        return LSQ_ECALLBACK;
+    }
+    return LSQ_OK;
+}
+
+// The first g! and the gradient + colsumabs2 pass of its Jacobian are queued behind the start residual BEFORE the host waits
+// for ssr and the check of x0 (the device used to stand idle for that round trip): the built-in model with LSMR.  A
+// non-finite x0 still leaves at the top of the first iteration, with the counts of a loop that never called g!; the
+// colsumabs2 formed for those factors is forgotten.
+struct LmAhead {
+    lsq_g_callback g; lsq_mat *J; const double *x; void *user; const double *fcur; double *grad;
+    bool g_done, grad_done;
+};
+static int lm_ahead(void *p) {
+    LmAhead &a = *(LmAhead *)p;
+    LSQ_TRY(call_g(a.g, a.J, a.x, a.user));
+    a.g_done = true;
+    if (a.J->colsum_version != a.J->version && lsq_can_fuse_grad_colsum(a.J)) {
+        LSQ_TRY(lsq_sparse_grad_colsum(a.J, a.fcur, a.grad));
+        a.grad_done = true;
+    }
+    return LSQ_OK;
+}
+
+// The gradient + colsumabs2 pass of the NEXT Jacobian may be queued behind an iteration's tail (spec_ok in optimize_lm_loop).
+// ready: that pass has run for the factors g! is about to install -- adopted at the head of the next iteration;
+// pending: a pass has been QUEUED and the host has not yet ruled on it (an error return between the two -- a departed
+// C5 peer, a failed wait, a callback failure -- must not leave another Jacobian's colsumabs2 marked current).
+// Either one still set when the loop is left: the pass is forgotten.
+namespace {
+struct SpecGuard {
+    lsq_mat *J;
+    bool &ready, &pending;
+    ~SpecGuard() { if (ready || pending) lsq_sparse_colsum_forget(J); }
+};
+}
+
+// active ranks: the iteration's one exchange (same values as at the top of the iteration: ssr and
+// the gradient norm change only at its end) runs on the host while the device is busy -- inside
+// the LSMR driver once its look-ahead window is full, else right behind the queued g!,
+// gradient and damping launches.  "all converged" cannot come back true: this rank itself is not.
+struct LmXchg { const lsq_options *o; double *gssr, *ggr; };
+static int lm_idle_exchange(void *p) {
+    LmXchg *q = (LmXchg *)p;
+    int all = 0;
+    return global_exchange(q->o, q->gssr, q->ggr, &all);
+}
+
+// What follows the solve -- x_trial = x - dx, the predicted residual |J dx - f|^2 (:114-117) and f!(x_trial) with its
+// sum of squares (:107, :111) -- depends on the solve only through dx.  With LSMR on the sliced layouts and a
+// device-side f! it is handed to the solve as its TAIL: enqueued right behind the inner iteration at which the
+// previous solve stopped, every kernel skipping itself if LSMR turns out not to be over by then (lsq_solver.h:
+// LsmrTail).  When the guess holds the device runs from the last inner iteration straight into the step kernel: no
+// early-exit launches of the look-ahead, no wait for the host to notice the stop.  (The predicted residual is formed
+// BEFORE f!(x_trial): it does not depend on it, and the row copy of J that the last LSMR iterations streamed is then
+// still partly in the Infinity Cache.)
+struct LmTail {
+    lsq_ctx *c; lsq_mat *J; LoopBuffers *b; lsq_f_callback f; void *user; const lsq_options *o;
+    const double *x, *fcur; double *xt, *ftrial;    // this iteration's iterate and trial buffers
+    int m, n, gn;
+    bool is_model;          // f! is the built-in model's, off the reference-order kernels
+    bool want_spec;         // queue the next Jacobian's gradient + colsumabs2 pass behind the pair kernel
+    double ssr;
+    bool *spec_pending;     // (SpecGuard)
+    LsqSlotPublish pub;     // out: the ticket the iteration's scalars arrive under
+    bool spec_launched;     // out: of the LAST time the tail was queued (an earlier one skipped itself)
+};
+static int lm_tail(const int *skip, void *u) {
+    LmTail &t = *(LmTail *)u;
+    lsq_ctx *c = t.c;
+    LSQ_TRY(launch_step(c, t.is_model, t.user, t.gn, t.n, t.x, t.b->dx, t.xt, skip));   // :106
+    // the last kernel of the iteration hands the scalars to the host
+    t.pub = lsq_slots_ticket(c, SL_GRAD, 6);      // (the sixth: whether the device let the queued pass run, k_sell_rows_pair)
+    bool pair = false;
+    SpecGrad sg{t.want_spec ? next_gate(c, *t.b) : nullptr, t.ssr, t.b->grad, false, t.o->x_tol, t.o->f_tol, t.o->g_tol};
+    if (t.is_model && model_pair_tail(t.user, t.J, t.b->dx, t.fcur, t.ftrial, t.xt, c->d_slots + SL_PRED, c->d_slots + SL_TRIAL,
+                                      t.pub, skip, &pair, &sg) != 0) {
+        lsq_set_error("user callback reported failure");
+        return LSQ_ECALLBACK;
+    }
+    t.spec_launched = sg.launched;
+    if (sg.launched) *t.spec_pending = true;
+    if (!pair) {
+        LSQ_TRY(predicted_to_slot(c, false, t.J, t.b->dx, t.fcur, t.b->fpred, 8, c->d_slots + SL_PRED, LsqSlotPublish(), skip));
+        LSQ_TRY(f_then_sumsq(c, false, t.f, t.user, t.m, t.ftrial, t.xt, 7, c->d_slots + SL_TRIAL, t.pub, skip));
+    }
+    LSQ_HIP(hipGetLastError());
+    return LSQ_OK;
+}
+
 static int optimize_lm_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat *J, double *x_user, double *fcur_user,
                             lsq_f_callback f, lsq_g_callback g, void *user, const lsq_options *o, lsq_result *r) {
     const int m = J->m, n = J->n;
@@ -793,23 +730,13 @@ static int optimize_lm_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat 
     // row-sharded single problem: J, fcur, ftrial are this rank's rows; sums over residuals are completed across the ranks
     // by the hook (a device buffer, in place, ordered on the stream) before the host reads them
     const bool sharded = o->row_allreduce != nullptr;
-    // The first g! and the gradient + colsumabs2 pass of its Jacobian are queued behind the start residual BEFORE the host waits
-    // for ssr and the check of x0 (the device used to stand idle for that round trip): the built-in model with LSMR.  A
-    // non-finite x0 still leaves at the top of the first iteration, with the counts of a loop that never called g!; the
-    // colsumabs2 formed for those factors is forgotten.
-    struct AheadCtx { lsq_g_callback g; lsq_mat *J; const double *x; void *user; const double *fcur; double *grad; bool g_done, grad_done; }
-        ah{g, J, x, user, fcur, b.grad, false, false};
-    const StartAhead ahead{[](void *p) -> int {
-        AheadCtx &a = *(AheadCtx *)p;
-        LSQ_TRY(call_g(a.g, a.J, a.x, a.user));
-        a.g_done = true;
-        if (a.J->colsum_version != a.J->version && lsq_can_fuse_grad_colsum(a.J)) {
-            LSQ_TRY(lsq_sparse_grad_colsum(a.J, a.fcur, a.grad));
-            a.grad_done = true;
-        }
-        return LSQ_OK;
-    }, &ah};
-    const bool ahead_ok = f == model_f && g == model_g && sv->kind == LSQ_LSMR && o->iterations > 0;
+    // (f AND g must be the built-in model's where a pass is queued for factors that g! has yet to install: the pass assumes that
+    //  g! installs what the start / step kernel has put into d_sspec -- lsq_model_f() is a public export and may be paired with
+    //  somebody else's g!)
+    const bool model_fg = model_is_builtin(f, g);
+    LmAhead ah{g, J, x, user, fcur, b.grad, false, false};
+    const StartAhead ahead{lm_ahead, &ah};
+    const bool ahead_ok = model_fg && sv->kind == LSQ_LSMR && o->iterations > 0;
     if (sharded) CB(f(fcur, x, user));
     else {
         const int st = start_residual(c, J, f, user, fcur, x, &ssr, &nonfinite_at,
@@ -819,16 +746,9 @@ static int optimize_lm_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat 
         LSQ_TRY(st);
     }
     f_calls++;
-    auto rows_sum = [&](double *d_buf, int count) -> int {
-        if (o->row_allreduce(d_buf, count, (void *)c->stream, o->row_allreduce_user) != 0) {
-            lsq_set_error("row all-reduce callback reported failure");
-            return LSQ_ECALLBACK;
-        }
-        return LSQ_OK;
-    };
     if (sharded) {
         LSQ_TRY(sumsq_to_slot(c, false, m, fcur, 7, c->d_slots + SL_TRIAL));
-        LSQ_TRY(rows_sum(c->d_slots + SL_TRIAL, 1));
+        LSQ_TRY(rows_sum(c, o, c->d_slots + SL_TRIAL, 1));
         LSQ_TRY(lsq_read_slots(c, SL_TRIAL, 1, &ssr));
         LSQ_TRY(lsq_first_nonfinite(c, n, x, &nonfinite_at));
     }
@@ -838,38 +758,28 @@ static int optimize_lm_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat 
     const int gn = ngrid(c, n);
     // reference summation order for small problems (lsq_exact.hip); a general preconditioner runs the operator-level LSMR
     const bool exact = lsq_small_mat(J) && !sharded && !(sv->kind == LSQ_LSMR && sv->gen_ldiv);
+    const bool is_model = !exact && model_is_builtin(f);     // (f! takes its fused passes and tanh(x_trial) from the step kernel)
     int last_inner = 0;          // inner iterations of the previous LSMR solve of this run: the guess for the next one (LsmrTail)
     // The gradient + colsumabs2 pass of the NEXT Jacobian queued behind the tail of this iteration, before the host has seen the
     // iteration's scalars (the ~12 us in which the host reads them, decides and launches used to be idle device time): the built-in
-    // model on a column-scaled handle with LSMR, no exchange.  spec_grad_ready: that pass has run for the factors g! is about to
-    // install -- adopted at the head of the next iteration, or forgotten if the loop is left before (SpecGuard).
+    // model on a column-scaled handle with LSMR, no exchange.
     const bool no_spec_grad = getenv("LSQ_NO_SPEC_GRADIENT") != nullptr;       // (read per run: the tests flip it)
-    // spec_pending: a pass has been QUEUED and the host has not yet ruled on it (an error return between the two --
-    // a departed C5 peer, a failed wait, a callback failure -- must not leave another Jacobian's colsumabs2 marked current)
     bool spec_launched = false, spec_grad_ready = false, spec_pending = false;
-    struct SpecGuard { lsq_mat *J; bool &ready; bool &pending; ~SpecGuard() { if (ready || pending) lsq_sparse_colsum_forget(J); } }
-        spec_guard{J, spec_grad_ready, spec_pending};
-    int local_done = 0;
+    SpecGuard spec_guard{J, spec_grad_ready, spec_pending};
     double gssr = ssr, ggr = maxabs_gr;
+    LmXchg xchg{o, &gssr, &ggr};
     long long inner_total = 0;
     while (iter < o->iterations) {
-        if (!o->allreduce && converged) break;
-        if (o->allreduce && converged) {
-            // frozen ranks keep taking part in the exchange until every problem has converged
-            int all = 1;
-            gssr = ssr; ggr = maxabs_gr;
-            LSQ_TRY(global_exchange(o, &gssr, &ggr, &all));
+        if (converged) {
+            if (!o->allreduce) break;
+            bool all;
+            LSQ_TRY(frozen_turn(o, ssr, maxabs_gr, &gssr, &ggr, &all));
             if (all) break;
-            ++iter; local_done = 1;
+            ++iter;
             continue;
         }
         iter++;
-        if (nonfinite_at >= 0) {  // check_isfinite(x), utils.jl:70-75
-            r->bad_index = nonfinite_at;
-            r->iterations = iter - 1;
-            lsq_set_error("IsFiniteException: non-finite x at index %d", nonfinite_at);
-            return LSQ_ENONFINITE;
-        }
+        if (nonfinite_at >= 0) return nonfinite_exit(r, nonfinite_at, iter);
         if (need_jac) {
             if (!ah.g_done) LSQ_TRY(call_g(g, J, x, user));     // (the first one may be queued already: see ahead)
             ah.g_done = false;
@@ -887,10 +797,9 @@ static int optimize_lm_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat 
         // (is a pass for the NEXT Jacobian worth queueing behind this iteration's tail?  not in the last allowed iteration)
         // (independent problems with their per-iteration exchange, C5, take it too: the exchange neither reads nor decides anything
         //  the pass depends on; a rank frozen after convergence never adopts -- SpecGuard forgets the pass when the loop is left)
-        // (f AND g must be the built-in model's: the pass assumes that g! installs the factors the step kernel has put into
-        //  d_sspec -- lsq_model_f() is a public export and may be paired with somebody else's g!)
-        const bool spec_ok = !no_spec_grad && !exact && !sharded && sv->kind == LSQ_LSMR && f == model_f && g == model_g &&
-                             iter < o->iterations && !lsq_dbg_serial;
+        // (f AND g must be the built-in model's: model_fg)
+        const bool spec_ok = !no_spec_grad && !exact && !sharded && sv->kind == LSQ_LSMR && model_fg && iter < o->iterations &&
+                             !lsq_dbg_serial;
         spec_launched = false;
         if (!exact && J->colsum_version != J->version && lsq_can_fuse_grad_colsum(J)) {
             LSQ_TRY(lsq_sparse_grad_colsum(J, fcur, b.grad));
@@ -910,7 +819,7 @@ static int optimize_lm_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat 
             // (into dtd); J and fcur do not change in between, so it is formed once, before the
             // solve, and LSMR's setup product A'b = P.*(J'f)/beta reuses it (saves one pass over J).
             if (!have_grad) LSQ_TRY(gradient_into(c, exact, J, fcur, b.grad));
-            if (sharded) LSQ_TRY(rows_sum(b.grad, n));                  // J'f = sum_p J_p'f_p
+            if (sharded) LSQ_TRY(rows_sum(c, o, b.grad, n));                 // J'f = sum_p J_p'f_p
             if (lm_prep) {}   // (damping and gradient norm ride in the LSMR setup launch below)
             else if (one_wg)
                 LSQ_LAUNCH(k_lm_damp_grad, dim3(1), dim3(1024), 0, c->stream, n, cs, 1.0 / delta, b.dtd, b.grad,
@@ -920,65 +829,16 @@ static int optimize_lm_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat 
                                    c->d_partials, lsq_ctr(c, 4), c->d_slots + SL_GRAD);
             mul_calls++;
         }
-        // active ranks: the iteration's one exchange (same values as at the top of the iteration: ssr and
-        // the gradient norm change only at its end) runs on the host while the device is busy -- inside
-        // the LSMR driver once its look-ahead window is full, else right here behind the queued g!,
-        // gradient and damping launches.  "all converged" cannot come back true: this rank itself is not.
-        struct Xchg { const lsq_options *o; double *gssr, *ggr; } xchg{o, &gssr, &ggr};
-        if (o->allreduce) {
+        if (o->allreduce) {     // active ranks: the iteration's one exchange, on the host while the device is busy (LmXchg)
             gssr = ssr; ggr = maxabs_gr;
-            c->idle_hook = [](void *p) -> int {
-                Xchg *q = (Xchg *)p;
-                int all = 0;
-                return global_exchange(q->o, q->gssr, q->ggr, &all);
-            };
+            c->idle_hook = lm_idle_exchange;
             c->idle_user = &xchg;
             c->idle_status = 0;
             if (sv->kind != LSQ_LSMR || exact) lsq_run_idle_hook(c);
         }
         int lmiter = 0;
-        // What follows the solve -- x_trial = x - dx, the predicted residual |J dx - f|^2 (:114-117) and f!(x_trial) with its
-        // sum of squares (:107, :111) -- depends on the solve only through dx.  With LSMR on the sliced layouts and a
-        // device-side f! it is handed to the solve as its TAIL: enqueued right behind the inner iteration at which the
-        // previous solve stopped, every kernel skipping itself if LSMR turns out not to be over by then (lsq_solver.h:
-        // LsmrTail).  When the guess holds the device runs from the last inner iteration straight into the step kernel: no
-        // early-exit launches of the look-ahead, no wait for the host to notice the stop.  (The predicted residual is formed
-        // BEFORE f!(x_trial): it does not depend on it, and the row copy of J that the last LSMR iterations streamed is then
-        // still partly in the Infinity Cache.)
-        struct TailCtx {
-            lsq_ctx *c; lsq_mat *J; LoopBuffers *b; lsq_f_callback f; void *user;
-            const double *x, *fcur; double *xt, *ftrial;
-            int m, n, gn; bool is_model; LsqSlotPublish pub; int launched;
-            bool want_spec; double ssr; bool spec_launched; bool *spec_pending; const lsq_options *o;
-        } tc{c, J, &b, f, user, x, fcur, xt, ftrial, m, n, gn, !exact && f == model_f, LsqSlotPublish(), 0, spec_ok, ssr, false,
-             &spec_pending, o};
-        auto tail_fn = [](const int *skip, void *u) -> int {
-            TailCtx &t = *(TailCtx *)u;
-            lsq_ctx *c = t.c;
-            double *t_out = nullptr, *s_out = nullptr;   // (the built-in model takes tanh(x_trial) from this launch)
-            if (t.is_model) model_trial_buffers(t.user, t.xt, &t_out, &s_out);
-            LSQ_LAUNCH(k_step, dim3(t.gn), dim3(LSQ_NT), 0, c->stream, t.n, t.x, t.b->dx, t.xt, c->d_partials,
-                               lsq_ctr(c, 5), c->d_slots + SL_DX, c->d_slots + SL_NONFIN, t_out, s_out, skip);   // :106
-            LSQ_HIP(hipGetLastError());
-            // the last kernel of the iteration hands the scalars to the host
-            t.pub = lsq_slots_ticket(c, SL_GRAD, 6);      // (the sixth: whether the device let the queued pass run, k_sell_rows_pair)
-            bool pair = false;
-            SpecGrad sg{t.want_spec ? next_gate(c, *t.b) : nullptr, t.ssr, t.b->grad, false, t.o->x_tol, t.o->f_tol, t.o->g_tol};
-            if (t.is_model && model_pair_tail(t.user, t.J, t.b->dx, t.fcur, t.ftrial, t.xt, c->d_slots + SL_PRED, c->d_slots + SL_TRIAL,
-                                              t.pub, skip, &pair, &sg) != 0) {
-                lsq_set_error("user callback reported failure");
-                return LSQ_ECALLBACK;
-            }
-            t.spec_launched = sg.launched;      // (of the LAST time the tail was queued: an earlier one skipped itself)
-            if (sg.launched) *t.spec_pending = true;
-            if (!pair) {
-                LSQ_TRY(predicted_to_slot(c, false, t.J, t.b->dx, t.fcur, t.b->fpred, 8, c->d_slots + SL_PRED, LsqSlotPublish(), skip));
-                LSQ_TRY(f_then_sumsq(c, false, t.f, t.user, t.m, t.ftrial, t.xt, 7, c->d_slots + SL_TRIAL, t.pub, skip));
-            }
-            LSQ_HIP(hipGetLastError());
-            t.launched++;
-            return LSQ_OK;
-        };
+        // the step, the predicted residual and f!(x_trial): handed to an LSMR solve as its tail, else queued behind the solve
+        LmTail tc{c, J, &b, f, user, o, x, fcur, xt, ftrial, m, n, gn, is_model, spec_ok, ssr, &spec_pending, LsqSlotPublish(), false};
         // (with the per-iteration exchange of independent problems too: the hook is issued by the LSMR driver while the device
         //  works off the queued iterations and the tail)
         const bool tail_ok = !exact && !sharded && sv->kind == LSQ_LSMR && !b.lo && !b.hi;
@@ -988,7 +848,7 @@ static int optimize_lm_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat 
             // (speculation needs kernels that honour the skip flag: the device model on the sliced rows)
             static const bool no_spec = getenv("LSQ_NO_TAIL_SPECULATION") != nullptr;
             const bool guardable = tc.is_model && J->kind == LSQ_MAT_CSC && J->srows.active && !no_spec && !lsq_dbg_serial;
-            LsmrTail tail{guardable ? last_inner : 0, tail_fn, &tc, guardable};
+            LsmrTail tail{guardable ? last_inner : 0, lm_tail, &tc, guardable};
             LSQ_TRY(lsq_lsmr_solve(sv, J, fcur, b.dtd, b.dx, &lmiter, b.grad, ssr, lm_prep ? &prep : nullptr,
                                    tail_ok ? &tail : nullptr));  // :87
             tail_done = tail_ok;
@@ -1003,7 +863,7 @@ static int optimize_lm_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat 
         if (!tail_done && !exact && !sharded) {
             // the solve was not handed the tail (bounds, or a factorisation): the same sequence, unguarded, behind the clipped step
             LSQ_TRY(lsq_box_clip(c, n, b.dx, x, b.lo, b.hi));                // :89-98
-            LSQ_TRY(tail_fn(nullptr, &tc));
+            LSQ_TRY(lm_tail(nullptr, &tc));
             tail_done = true;
         }
         if (tail_done) {
@@ -1012,12 +872,8 @@ static int optimize_lm_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat 
             LSQ_TRY(lsq_wait_slots(c, SL_GRAD, 6, tc.pub.seq, sl));
         } else {
             LSQ_TRY(lsq_box_clip(c, n, b.dx, x, b.lo, b.hi));                // :89-98
-            double *t_out = nullptr, *s_out = nullptr;   // (the built-in model takes tanh(x_trial) from this launch)
-            if (!exact && f == model_f) model_trial_buffers(user, xt, &t_out, &s_out);
-            LSQ_LAUNCH(k_step, dim3(gn), dim3(LSQ_NT), 0, c->stream, n, x, b.dx, xt, c->d_partials,
-                               lsq_ctr(c, 5), c->d_slots + SL_DX, c->d_slots + SL_NONFIN, t_out, s_out);   // :106
-            LSQ_HIP(hipGetLastError());
-            if (exact) {
+            LSQ_TRY(launch_step(c, is_model, user, gn, n, x, b.dx, xt));       // :106
+            if (exact) {                                                      // the reference's order
                 CB(f(ftrial, xt, user));                                      // :107
                 f_calls++;
                 LSQ_TRY(sumsq_to_slot(c, exact, m, ftrial, 7, c->d_slots + SL_TRIAL));                 // :111
@@ -1031,7 +887,7 @@ static int optimize_lm_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat 
                 LSQ_TRY(predicted_to_slot(c, exact, J, b.dx, fcur, b.fpred, 8, c->d_slots + SL_PRED));
                 LSQ_TRY(f_then_sumsq(c, exact, f, user, m, ftrial, xt, 7, c->d_slots + SL_TRIAL));
                 f_calls++;
-                LSQ_TRY(rows_sum(c->d_slots + SL_TRIAL, 2));
+                LSQ_TRY(rows_sum(c, o, c->d_slots + SL_TRIAL, 2));
                 LSQ_TRY(lsq_read_slots(c, SL_GRAD, 5, sl));
             }
         }
@@ -1073,27 +929,18 @@ static int optimize_lm_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat 
         }
         record(o, c, iter, n, ssr, maxabs_gr, delta, rho, lmiter, accepted ? 1 : 0, x);
     }
-    (void)local_done;
-    LSQ_HIP(hipStreamSynchronize(c->stream));
-    r->optimizer = LSQ_LEVENBERG_MARQUARDT;
-    r->ssr = o->allreduce ? gssr : ssr;
-    r->iterations = iter;
-    r->converged = converged; r->x_converged = xc; r->f_converged = fc; r->g_converged = gc;
-    r->f_calls = f_calls; r->g_calls = g_calls; r->mul_calls = mul_calls;
-    r->lsmr_iterations = inner_total;
-    return LSQ_OK;
+    return finish_result(c, r, LSQ_LEVENBERG_MARQUARDT, o->allreduce ? gssr : ssr, iter, converged,
+                         LoopTally{f_calls, g_calls, mul_calls, xc, fc, gc, inner_total});
+}
+static int optimize_lm(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat *J, double *x_user, double *fcur_user,
+                       lsq_f_callback f, lsq_g_callback g, void *user, const lsq_options *o, lsq_result *r) {
+    ShardedExit ex{c, o};
+    return ex.finish(optimize_lm_loop(c, sv, b, J, x_user, fcur_user, f, g, user, o, r));
 }
 
 // ---------------------------------------------------------------------------------------------
 // dogleg.jl:41-203
 // ---------------------------------------------------------------------------------------------
-static int optimize_dogleg_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat *J, double *x, double *fcur,
-                                lsq_f_callback f, lsq_g_callback g, void *user, const lsq_options *o, lsq_result *r);
-static int optimize_dogleg(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat *J, double *x, double *fcur,
-                           lsq_f_callback f, lsq_g_callback g, void *user, const lsq_options *o, lsq_result *r) {
-    ShardedExit ex{c, o};
-    return ex.finish(optimize_dogleg_loop(c, sv, b, J, x, fcur, f, g, user, o, r));
-}
 static int optimize_dogleg_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat *J, double *x_user, double *fcur_user,
                                 lsq_f_callback f, lsq_g_callback g, void *user, const lsq_options *o, lsq_result *r) {
     const int m = J->m, n = J->n;
@@ -1111,25 +958,20 @@ static int optimize_dogleg_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_
     double maxabs_gr = INFINITY;
     const int gn = ngrid(c, n);
     const bool exact = lsq_small_mat(J);
+    const bool is_model = !exact && model_is_builtin(f);     // (f! takes tanh(x_trial) from the step kernel)
     double gssr = ssr, ggr = maxabs_gr;
     long long inner_total = 0;
     while (iter < o->iterations) {
-        if (!o->allreduce && converged) break;
-        if (o->allreduce && converged) {   // frozen rank (see optimize_lm)
-            int all = 1;
-            gssr = ssr; ggr = maxabs_gr;
-            LSQ_TRY(global_exchange(o, &gssr, &ggr, &all));
+        if (converged) {
+            if (!o->allreduce) break;
+            bool all;
+            LSQ_TRY(frozen_turn(o, ssr, maxabs_gr, &gssr, &ggr, &all));
             if (all) break;
             ++iter;
             continue;
         }
         iter++;
-        if (nonfinite_at >= 0) {
-            r->bad_index = nonfinite_at;
-            r->iterations = iter - 1;
-            lsq_set_error("IsFiniteException: non-finite x at index %d", nonfinite_at);
-            return LSQ_ENONFINITE;
-        }
+        if (nonfinite_at >= 0) return nonfinite_exit(r, nonfinite_at, iter);
         int ls_iter = 0;
         bool exchanged = false;
         if (!reuse) {
@@ -1209,11 +1051,7 @@ static int optimize_dogleg_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_
             wnorm_dx = std::sqrt(w2);
         }
         LSQ_TRY(lsq_box_clip(c, n, b.dx, x, b.lo, b.hi));                 // :148-160
-        double *t_out = nullptr, *s_out = nullptr;   // (the built-in model takes tanh(x_trial) from this launch)
-        if (!exact && f == model_f) model_trial_buffers(user, xt, &t_out, &s_out);
-        LSQ_LAUNCH(k_step, dim3(gn), dim3(LSQ_NT), 0, c->stream, n, x, b.dx, xt, c->d_partials,
-                           lsq_ctr(c, 5), c->d_slots + SL_DX, c->d_slots + SL_NONFIN, t_out, s_out);    // :160
-        LSQ_HIP(hipGetLastError());
+        LSQ_TRY(launch_step(c, is_model, user, gn, n, x, b.dx, xt));                       // :160
         LSQ_TRY(f_then_sumsq(c, exact, f, user, m, ftrial, xt, 7, c->d_slots + SL_TRIAL));   // :164, :168
         f_calls++;
         LSQ_TRY(predicted_to_slot(c, exact, J, b.dx, fcur, b.fpred, 8, c->d_slots + SL_PRED));  // :171-174
@@ -1242,14 +1080,13 @@ static int optimize_dogleg_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_
         else if (rho > INCREASE_THRESHOLD) delta = std::max(delta, 3.0 * wnorm_dx);
         record(o, c, iter, n, ssr, maxabs_gr, delta, rho, ls_iter, accepted ? 1 : 0, x);
     }
-    LSQ_HIP(hipStreamSynchronize(c->stream));
-    r->optimizer = LSQ_DOGLEG;
-    r->ssr = o->allreduce ? gssr : ssr;
-    r->iterations = iter;
-    r->converged = converged; r->x_converged = xc; r->f_converged = fc; r->g_converged = gc;
-    r->f_calls = f_calls; r->g_calls = g_calls; r->mul_calls = mul_calls;
-    r->lsmr_iterations = inner_total;
-    return LSQ_OK;
+    return finish_result(c, r, LSQ_DOGLEG, o->allreduce ? gssr : ssr, iter, converged,
+                         LoopTally{f_calls, g_calls, mul_calls, xc, fc, gc, inner_total});
+}
+static int optimize_dogleg(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat *J, double *x, double *fcur,
+                           lsq_f_callback f, lsq_g_callback g, void *user, const lsq_options *o, lsq_result *r) {
+    ShardedExit ex{c, o};
+    return ex.finish(optimize_dogleg_loop(c, sv, b, J, x, fcur, f, g, user, o, r));
 }
 
 extern "C" int lsq_optimize(lsq_ctx *c, int optimizer, int solver_kind, lsq_mat *J, double *x, double *fcur,
@@ -1330,519 +1167,4 @@ extern "C" int lsq_optimize(lsq_ctx *c, int optimizer, int solver_kind, lsq_mat 
     res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     res->status = st;
     return st;
-}
-
-// ---------------------------------------------------------------------------------------------
-// built-in model: r(x) = A tanh(x) - b ; J = A diag(1 - tanh(x)^2)      
-// ---------------------------------------------------------------------------------------------
-struct lsq_model {
-    lsq_ctx *ctx;
-    lsq_mat *J;
-    // fused: J is a COLUMN-SCALED handle on the sliced layouts (lsq_mat_set_colscale): J's own storage holds A once, g! writes
-    // the n factors s = 1 - tanh(x)^2 and nothing else; every product applies them on the fly
-    bool fused = false;
-    double *d_Acsc = nullptr;  // A values, CSC order (or dense column-major)                       } not fused: J's values are
-    double *d_Acsr = nullptr;  // A values in J's row-mirror layout (CSR order or sliced rows)      } multiplied out by g!
-    double *d_Ab = nullptr;    // A values in J's column-mirror layout (window-blocked CSC or sliced columns)
-    double *d_b = nullptr;
-    double *d_t = nullptr;     // tanh(x) of the latest f!
-    double *d_s = nullptr;     // 1 - tanh(x)^2 of the latest g! (fused: this IS J's column scale)
-    double *d_sspec = nullptr; // the same at the latest trial point (written by the step kernel)
-    const double *tanh_x = nullptr;   // device vector whose tanh the step kernel has already put into d_t
-    const double *sfac_x = nullptr;   // device vector whose 1 - tanh^2 the step kernel has already put into d_sspec
-    // k_sell_rows_pair reads its two m-vectors in the SLICE ORDER of J's sliced rows (lsq_sell.h): b once, and two mirrors of
-    // residual vectors, each valid for the row-order device vector named in perm_of (nullptr: stale)
-    double *d_b_perm = nullptr;
-    double *d_perm[2] = {nullptr, nullptr};
-    const double *perm_of[2] = {nullptr, nullptr};
-    long long pair_tails = 0;  // launches of k_sell_rows_pair (lsq_model_paths)
-};
-static void model_perm_invalidate(lsq_model *md, const double *vec) {   // vec == nullptr: all
-    for (int k = 0; k < 2; ++k)
-        if (!vec || md->perm_of[k] == vec) md->perm_of[k] = nullptr;
-}
-
-__global__ void __launch_bounds__(LSQ_NT) k_tanh(int n, const double *__restrict__ x, double *__restrict__ t) {
-    for (int i = blockIdx.x * LSQ_NT + threadIdx.x; i < n; i += gridDim.x * LSQ_NT) t[i] = tanh(x[i]);
-}
-
-struct EpiResidual {  // out = A t - b
-    static constexpr bool REDUCE = false;
-    const int *done;
-    int extra_blocks;
-    const double *b;
-    double *out;
-    double *partials;
-    unsigned *counter;
-    __device__ void seg(int i, double dot, double &) const { out[i] = dot - b[i]; }
-    using has_pre = void;
-    __device__ double pre(int i) const { return b[i]; }
-    __device__ void seg_pre(int i, double dot, double bi, double &) const { out[i] = dot - bi; }
-    __device__ void extra(int, double &) const {}
-    __device__ void finalize(double) const {}
-};
-
-struct EpiResidualSq {  // out = A t - b, and sum(out.^2) -> slot (+ the iteration's scalars to the host, like EpiPredict)
-    static constexpr bool REDUCE = true;
-    const int *done;
-    int extra_blocks;
-    const double *b;
-    double *out;
-    double *partials;
-    unsigned *counter;
-    double *slot;
-    LsqSlotPublish pub;
-    __device__ void seg(int i, double dot, double &racc) const { seg_pre(i, dot, b[i], racc); }
-    using has_pre = void;
-    __device__ double pre(int i) const { return b[i]; }
-    __device__ void seg_pre(int i, double dot, double bi, double &racc) const {
-        const double v = dot - bi;
-        out[i] = v;
-        racc += v * v;
-    }
-    __device__ void extra(int, double &) const {}
-    __device__ void finalize(double t) const {
-        *slot = t;
-        if (pub.count > 0) {
-            for (int i = 0; i < pub.count; ++i)
-                __hip_atomic_store(pub.dst + i, pub.src + i == slot ? t : pub.src[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(pub.seq_word, pub.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-};
-
-// ... and the same residual in the SLICE ORDER of the sliced rows (what k_sell_rows_pair reads: SellPairEpi), stored by the lane
-// that formed the row's sum: out_perm[s * 64 + lane] = dot - b_perm[s * 64 + lane], the bits of out[row]
-struct EpiResidualSqPerm : EpiResidualSq {
-    const double *b_perm;
-    double *out_perm;
-    using has_slice_out = void;
-    __device__ double slice_pre(size_t pidx) const { return b_perm[pidx]; }
-    __device__ void slice_post(size_t pidx, double dot, double bi) const { out_perm[pidx] = dot - bi; }
-};
-
-// column scaling of a column-segmented value array (CSC nzval or dense columns)
-__global__ void __launch_bounds__(LSQ_NT)
-k_scale_cols(int n, const int *__restrict__ colptr, int m_dense, const double *__restrict__ A,
-             const double *__restrict__ x, double *__restrict__ out) {
-    for (int j = blockIdx.x; j < n; j += gridDim.x) {
-        double t = tanh(x[j]);
-        double s = 1.0 - t * t;
-        long long k0 = colptr ? colptr[j] : (long long)j * m_dense;
-        long long k1 = colptr ? colptr[j + 1] : (long long)(j + 1) * m_dense;
-        for (long long k = k0 + threadIdx.x; k < k1; k += LSQ_NT) out[k] = A[k] * s;
-    }
-}
-// dense J = A diag(1 - tanh(x)^2): block (column j, row chunk)
-__global__ void __launch_bounds__(LSQ_NT)
-k_scale_dense(int m, const double *__restrict__ A, const double *__restrict__ x, double *__restrict__ out) {
-    const int j = blockIdx.x;
-    const double t = tanh(x[j]);
-    const double sfac = 1.0 - t * t;
-    const size_t base = (size_t)j * m;
-    for (int i = blockIdx.y * LSQ_NT + threadIdx.x; i < m; i += gridDim.y * LSQ_NT) out[base + i] = A[base + i] * sfac;
-}
-// the CSR mirror: scale by the column of each entry
-__global__ void __launch_bounds__(LSQ_NT)
-k_scale_csr(long long nnz, const int *__restrict__ colidx, const double *__restrict__ A, const double *__restrict__ sfac,
-            double *__restrict__ out) {
-    for (long long k = blockIdx.x * (long long)LSQ_NT + threadIdx.x; k < nnz; k += (long long)gridDim.x * LSQ_NT)
-        out[k] = A[k] * sfac[colidx[k]];
-}
-// the start point of a solve: t = tanh(x), s = 1 - tanh(x)^2 (k_tanh and k_sfac, the same expressions) and check_isfinite(x)
-// (k_first_nonfinite, the same code) in one launch
-__global__ void __launch_bounds__(LSQ_NT) k_tanh_sfac(int n, const double *__restrict__ x, double *__restrict__ t,
-                                                      double *__restrict__ s, double *partials, unsigned *counter,
-                                                      double *out_nonfin) {
-    __shared__ double sh[LSQ_NT / 64];
-    double code = 0.0;
-    for (int i = blockIdx.x * LSQ_NT + threadIdx.x; i < n; i += gridDim.x * LSQ_NT) {
-        const double xi = x[i];
-        const double v = tanh(xi);
-        t[i] = v;
-        s[i] = 1.0 - v * v;
-        if (!isfinite(xi) && code == 0.0) code = 1e15 - (double)(i + 1);
-    }
-    const double bv = block_max<LSQ_NT>(code, sh);
-    grid_reduce<LSQ_NT, true>(bv, partials, counter, gridDim.x, sh, [=](double m) {
-        *out_nonfin = (m == 0.0) ? -1.0 : (1e15 - m) - 1.0;
-    });
-}
-__global__ void __launch_bounds__(LSQ_NT) k_sfac(int n, const double *__restrict__ x, double *__restrict__ s) {
-    for (int i = blockIdx.x * LSQ_NT + threadIdx.x; i < n; i += gridDim.x * LSQ_NT) {
-        double t = tanh(x[i]);
-        s[i] = 1.0 - t * t;
-    }
-}
-
-// window-blocked CSC: segment s belongs to column s % n; one wave per segment
-__global__ void __launch_bounds__(LSQ_NT)
-k_scale_bcsc(int nseg, int n, const int *__restrict__ ptr, const double *__restrict__ A, const double *__restrict__ sfac,
-             double *__restrict__ out) {
-    const int lane = threadIdx.x & 63, per = LSQ_NT / 64;
-    for (int s = blockIdx.x * per + (threadIdx.x >> 6); s < nseg; s += gridDim.x * per) {
-        const double f = sfac[s % n];
-        const int k1 = ptr[s + 1];
-        for (int k = ptr[s] + lane; k < k1; k += 64) out[k] = A[k] * f;
-    }
-}
-
-// out[k] = A[k] * sfac[col16[k]] with the n scale factors staged in LDS: pure streaming
-// (16-byte value loads/stores, 8-byte index loads), one persistent 1024-thread workgroup per CU.
-// NT: the output is stored non-temporally (16-byte vector stores: 4.8 TB/s instead of 3.8 -- no
-// write-allocate next to the A stream); used for the copy that is not read back right away.
-typedef double lsq_d2 __attribute__((ext_vector_type(2)));
-template <bool NT>
-__global__ void __launch_bounds__(1024)
-k_scale_lds(long long nnz4, const unsigned short *__restrict__ col16, const double *__restrict__ A,
-            const double *__restrict__ sfac, int n, double *__restrict__ out) {
-    extern __shared__ double sf[];
-    // (the factors 1 - tanh(x)^2 come from k_sfac: ten fp64 tanh per thread in every one of the 256
-    //  workgroups cost ~6 us before the first byte was streamed)
-    for (int i = threadIdx.x; i < n; i += 1024) sf[i] = sfac[i];
-    __syncthreads();
-    for (long long q = blockIdx.x * 1024LL + threadIdx.x; q < nnz4; q += (long long)gridDim.x * 1024) {
-        const long long k = 4 * q;  // arrays are padded to a multiple of 4 (+8)
-        const lsq_d2 a0 = *reinterpret_cast<const lsq_d2 *>(A + k);
-        const lsq_d2 a1 = *reinterpret_cast<const lsq_d2 *>(A + k + 2);
-        const uint2 c = *reinterpret_cast<const uint2 *>(col16 + k);
-        lsq_d2 o0, o1;
-        o0.x = a0.x * sf[c.x & 0xffffu];
-        o0.y = a0.y * sf[c.x >> 16];
-        o1.x = a1.x * sf[c.y & 0xffffu];
-        o1.y = a1.y * sf[c.y >> 16];
-        if constexpr (NT) {
-            __builtin_nontemporal_store(o0, reinterpret_cast<lsq_d2 *>(out + k));
-            __builtin_nontemporal_store(o1, reinterpret_cast<lsq_d2 *>(out + k + 2));
-        } else {
-            *reinterpret_cast<lsq_d2 *>(out + k) = o0;
-            *reinterpret_cast<lsq_d2 *>(out + k + 2) = o1;
-        }
-    }
-}
-
-// short segments (LDS-window plan: ~4 entries): one thread per segment
-__global__ void __launch_bounds__(LSQ_NT)
-k_scale_bcsc_thread(int nseg, int n, const int *__restrict__ ptr, const double *__restrict__ A,
-                    const double *__restrict__ sfac, double *__restrict__ out) {
-    for (int s = blockIdx.x * LSQ_NT + threadIdx.x; s < nseg; s += gridDim.x * LSQ_NT) {
-        const double f = sfac[s % n];
-        const int k1 = ptr[s + 1];
-        for (int k = ptr[s]; k < k1; ++k) out[k] = A[k] * f;
-    }
-}
-
-static int model_f(double *out, const double *x, void *user) {
-    lsq_model *md = (lsq_model *)user;
-    lsq_ctx *c = md->ctx;
-    lsq_mat *J = md->J;
-    const bool have_tanh = md->tanh_x == x;   // the step kernel formed tanh(x) while it wrote x (model_trial_buffers)
-    md->tanh_x = nullptr;
-    model_perm_invalidate(md, out);           // (a slice-order mirror of `out` is stale from here on)
-    if (!have_tanh) {
-        md->sfac_x = nullptr;
-        LSQ_LAUNCH(k_tanh, dim3(ngrid(c, J->n)), dim3(LSQ_NT), 0, c->stream, J->n, x, md->d_t);
-    }
-    EpiResidual e{nullptr, 0, md->d_b, out, nullptr, nullptr};
-    if (J->kind == LSQ_MAT_CSC && J->srows.active) {
-        // the stored values themselves (fused: J's storage IS A; else A in the same layout), no column scale: r = A t - b
-        if (launch_sell_rows(J, nullptr, md->d_t, e, md->fused ? nullptr : md->d_Acsr) != LSQ_OK) return 1;
-    } else if (J->kind == LSQ_MAT_CSC) {
-        LsqSegs A = J->csr;  // same pattern, A's values
-        A.d_val = md->d_Acsr;
-        if (launch_segs<false>(c, A, md->d_t, e) != LSQ_OK) return 1;
-    } else {
-        lsq_mat tmp = *J;
-        tmp.d_dense = md->d_Acsc;
-        if (launch_product(&tmp, 0, md->d_t, e) != LSQ_OK) return 1;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : 1;
-}
-
-// the step kernel of both loops writes tanh(x_trial) and 1 - tanh(x_trial)^2 next to x_trial itself: the model's f!(., x_trial)
-// and -- if the step is accepted -- its g!(., x_trial) then need no n-length launch of their own
-static void model_trial_buffers(void *user, const double *xt, double **t_out, double **s_out) {
-    lsq_model *md = (lsq_model *)user;
-    md->tanh_x = md->sfac_x = nullptr;
-    if ((md->J->kind == LSQ_MAT_CSC && md->J->srows.active) || md->J->kind == LSQ_MAT_DENSE) {
-        *t_out = md->d_t;
-        *s_out = md->d_sspec;
-        md->tanh_x = md->sfac_x = xt;
-    }
-}
-
-static int model_start_point(void *user, const double *x, double *d_nonfin, bool *done) {
-    lsq_model *md = (lsq_model *)user;
-    lsq_ctx *c = md->ctx;
-    lsq_mat *J = md->J;
-    *done = false;
-    md->tanh_x = md->sfac_x = nullptr;
-    if (!(J->kind == LSQ_MAT_CSC && J->srows.active) || J->n <= 0) return 0;
-    LSQ_LAUNCH(k_tanh_sfac, dim3(ngrid(c, J->n)), dim3(LSQ_NT), 0, c->stream, J->n, x, md->d_t, md->d_sspec, c->d_partials,
-               lsq_ctr(c, 0), d_nonfin);
-    if (hipGetLastError() != hipSuccess) return 1;
-    md->tanh_x = md->sfac_x = x;      // (as model_trial_buffers records them for the step kernel)
-    *done = true;
-    return 0;
-}
-static void model_forget_point(void *user) {
-    lsq_model *md = (lsq_model *)user;
-    md->tanh_x = md->sfac_x = nullptr;
-}
-
-// does model_pair_tail apply to this handle (its conditions on the model and the layout; the caller adds those on the vectors)
-static bool model_pair_applies(const lsq_model *md, const lsq_mat *J) {
-    return md->fused && J == md->J && J->kind == LSQ_MAT_CSC && J->srows.active && J->srows.ncw == 1 && J->d_colscale &&
-           J->n <= LSQ_PAIR_X_MAX && !getenv("LSQ_NO_PAIR_TAIL");
-}
-// the slice-order buffers of model_pair_tail: b once per model, two mirrors of residual vectors.  false: they could not be
-// allocated (the callers take the paths that do without)
-static bool model_perm_ready(lsq_model *md) {
-    if (md->d_b_perm) return true;
-    lsq_ctx *c = md->ctx;
-    const LsqSell &S = md->J->srows;
-    const size_t plen = (size_t)S.nslices * 64;
-    const int pgrid = std::max(1, std::min(lsq_div_up((long long)plen, LSQ_NT), c->num_cus * 8));
-    double *pb = nullptr, *p0 = nullptr, *p1 = nullptr;     // (all three or none: a partial set must not look initialised)
-    if (hipMalloc(&pb, plen * sizeof(double)) != hipSuccess || hipMalloc(&p0, plen * sizeof(double)) != hipSuccess ||
-        hipMalloc(&p1, plen * sizeof(double)) != hipSuccess) {
-        (void)hipGetLastError();
-        hipFree(pb); hipFree(p0); hipFree(p1);
-        return false;
-    }
-    md->d_b_perm = pb; md->d_perm[0] = p0; md->d_perm[1] = p1;
-    LSQ_LAUNCH(k_sell_perm_rows<0>, dim3(pgrid), dim3(LSQ_NT), 0, c->stream, sell_dev(S), S.wrows, S.nslices, (const double *)md->d_b,
-               md->d_b_perm);
-    return true;
-}
-
-// f! + sum(abs2, out) in one pass (sliced rows only; *done tells whether it applied)
-static int model_f_sumsq(void *user, double *out, const double *x, int ctr, double *d_out, LsqSlotPublish pub, bool *done,
-                         const int *skip, bool mirror) {
-    lsq_model *md = (lsq_model *)user;
-    lsq_ctx *c = md->ctx;
-    lsq_mat *J = md->J;
-    *done = false;
-    if (!(J->kind == LSQ_MAT_CSC && J->srows.active)) return model_f(out, x, user);
-    model_perm_invalidate(md, out);
-    EpiResidualSq e{skip, 0, md->d_b, out, c->d_partials, lsq_ctr(c, ctr), d_out, pub};
-    const bool have_tanh = md->tanh_x == x;   // k_step (or k_tanh_sfac at the start point) formed tanh(x)
-    md->tanh_x = nullptr;
-    if (!have_tanh) {
-        md->sfac_x = nullptr;
-        LSQ_LAUNCH(k_tanh, dim3(ngrid(c, J->n)), dim3(LSQ_NT), 0, c->stream, J->n, x, md->d_t);
-    }
-    if (mirror && !skip && model_pair_applies(md, J) && model_perm_ready(md)) {
-        EpiResidualSqPerm ep;
-        static_cast<EpiResidualSq &>(ep) = e;
-        ep.b_perm = md->d_b_perm;
-        ep.out_perm = md->d_perm[0];
-        if (launch_sell_rows(J, nullptr, md->d_t, ep, nullptr) != LSQ_OK) return 1;
-        md->perm_of[0] = out;       // (model_pair_tail finds it there; perm_of[1] names another vector or nothing: `out` was invalidated)
-    } else if (launch_sell_rows(J, nullptr, md->d_t, e, md->fused ? nullptr : md->d_Acsr) != LSQ_OK) return 1;
-    *done = true;
-    return hipGetLastError() == hipSuccess ? 0 : 1;
-}
-
-static int model_pair_tail(void *user, lsq_mat *J, const double *dx, const double *fcur, double *ftrial, const double *xt,
-                           double *slot_pred, double *slot_trial, LsqSlotPublish pub, const int *skip, bool *done, SpecGrad *sg) {
-    lsq_model *md = (lsq_model *)user;
-    lsq_ctx *c = md->ctx;
-    *done = false;
-    // the column-scaled handle on the one-window sliced rows (J = A diag(s): both products stream the same A), both gather
-    // vectors resident in LDS, tanh(x_trial) already formed by the step kernel
-    if (!(model_pair_applies(md, J) && md->tanh_x == xt)) return 0;
-    const LsqSell &S = J->srows;
-    const int nxpad = (J->n + 1) & ~1;
-    // (two gather vectors; after a block's stream their LDS is the output window of its LSQ_SELL_ROWS_MAX rows)
-    const size_t lds = (size_t)std::max(2 * nxpad, LSQ_SELL_ROWS_MAX) * sizeof(double);
-    if (lsq_set_lds(c, (const void *)k_sell_rows_pair<0>, (size_t)2 * LSQ_PAIR_X_MAX * sizeof(double)) != LSQ_OK) return 0;
-    // slice-order mirrors: b once; f from the slot that mirrors fcur (filled by an earlier launch of this kernel if the step that
-    // produced fcur was accepted, else permuted now); the other slot takes this launch's trial residual
-    const size_t plen = (size_t)S.nslices * 64;
-    const int pgrid = std::max(1, std::min(lsq_div_up((long long)plen, LSQ_NT), c->num_cus * 8));
-    if (!model_perm_ready(md)) return 0;                        // (the caller takes the two-pass tail)
-    int k = md->perm_of[0] == fcur ? 0 : (md->perm_of[1] == fcur ? 1 : -1);
-    if (k < 0) {
-        k = 0;
-        LSQ_LAUNCH(k_sell_perm_rows<0>, dim3(pgrid), dim3(LSQ_NT), 0, c->stream, sell_dev(S), S.wrows, S.nslices, fcur, md->d_perm[k]);
-        md->perm_of[k] = fcur;
-    }
-    md->perm_of[1 - k] = ftrial;
-    md->tanh_x = nullptr;     // (consumed, as model_f_sumsq does)
-    const int grid = std::max(1, std::min(S.nblocks, c->num_cus));
-    // (the step kernel has put 1 - tanh^2(x_trial) into d_sspec: the factors g! will install if the step is accepted)
-    const bool spec = sg && sg->gate && md->sfac_x == xt;
-    SellPairEpi e{skip, md->d_perm[k], md->d_b_perm, ftrial, md->d_perm[1 - k], c->d_partials, c->d_partials + 4096, lsq_ctr(c, 7),
-                  slot_pred, slot_trial, pub, spec ? sg->gate : nullptr, spec ? sg->ssr : 0.0, MIN_STEP_QUALITY,
-                  c->d_slots + SL_SSR, c->d_slots + SL_DX, c->d_slots + SL_GRAD, spec ? sg->xtol : 0.0, spec ? sg->ftol : 0.0,
-                  spec ? sg->gtol : 0.0};
-    LSQ_LAUNCH(k_sell_rows_pair<0>, dim3(grid), dim3(LSQ_BIG_NT), lds, c->stream, sell_dev(S), S.wrows, J->m, dx, J->d_colscale,
-               (const double *)md->d_t, J->n, nxpad, e);
-    *done = true;
-    ++md->pair_tails;
-    if (hipGetLastError() != hipSuccess) return 1;
-    if (spec) {
-        const int st = lsq_sparse_grad_colsum_spec(J, ftrial, sg->grad, md->d_sspec, sg->gate);
-        if (st == LSQ_OK) sg->launched = true;
-        else if (st != LSQ_EARG) return 1;
-    }
-    return 0;
-}
-
-static int model_g(lsq_mat *J, const double *x, void *user) {
-    lsq_model *md = (lsq_model *)user;
-    lsq_ctx *c = md->ctx;
-    // s = 1 - tanh(x)^2: already there if x is the trial point the step kernel has just written (dense columns: k_scale_dense
-    // forms the factor of its column from x itself)
-    if (J->kind == LSQ_MAT_DENSE) {}
-    else if (md->sfac_x == x) std::swap(md->d_s, md->d_sspec);
-    else LSQ_LAUNCH(k_sfac, dim3(ngrid(c, J->n)), dim3(LSQ_NT), 0, c->stream, J->n, x, md->d_s);
-    md->sfac_x = nullptr;
-    md->tanh_x = nullptr;
-    if (md->fused) {
-        // J = A diag(s) is never multiplied out: handing the handle its (new) factor vector is all of g!
-        if (lsq_mat_set_colscale(J, md->d_s) != LSQ_OK) return 1;
-        return hipGetLastError() == hipSuccess ? 0 : 1;
-    }
-    if (J->kind == LSQ_MAT_CSC) {
-        // mirrors the products read: rows (CSR or sliced rows) and columns (window-blocked CSC or sliced
-        // columns), each with a 16-bit column per stored entry when the LDS-staged scaling applies
-        const bool have_cols = J->scols.active || J->nwin > 1;
-        const unsigned short *rcol = J->srows.active ? J->srows.d_idx16 : J->csr.d_idx16;
-        const unsigned short *ccol = J->scols.active ? J->scols.d_col16 : J->bcsc.d_col16;
-        double *rval = J->srows.active ? J->srows.d_val : J->csr.d_val;
-        double *cval = J->scols.active ? J->scols.d_val : J->bcsc.d_val;
-        const long long rlen = lsq_mirror_rows_len(J), clen = lsq_mirror_cols_len(J);
-        const bool lds_ok = J->n <= 12000 && J->nnz >= (1 << 20) && J->srows.ncw == 1;   // (window-relative indices otherwise)
-        // big problems: every product (and colsumabs2) reads the mirrors, so only those are written; the
-        // CSC-ordered copy is rebuilt on demand (lsq_ensure_csc)
-        const bool lazy_csc = lds_ok && rcol && have_cols && ccol && lsq_can_fuse_grad_colsum(J);
-        if (!lazy_csc) {
-            int grid = J->n < c->num_cus * 16 ? (J->n > 0 ? J->n : 1) : c->num_cus * 16;
-            LSQ_LAUNCH(k_scale_cols, dim3(grid), dim3(LSQ_NT), 0, c->stream, J->n, J->csc.d_ptr, 0, md->d_Acsc,
-                               x, J->csc.d_val);
-        }
-        J->csc_fresh = !lazy_csc;
-        const size_t lds = (size_t)J->n * sizeof(double);
-        if (lds_ok) {
-            LSQ_TRY(lsq_set_lds(c, (const void *)k_scale_lds<true>, 12000 * 8));
-            LSQ_TRY(lsq_set_lds(c, (const void *)k_scale_lds<false>, 12000 * 8));
-        }
-        if (J->nnz > 0) {
-            if (lds_ok && rcol) {
-                LSQ_LAUNCH(k_scale_lds<true>, dim3(c->num_cus), dim3(1024), lds, c->stream, (rlen + 3) / 4, rcol,
-                                   md->d_Acsr, md->d_s, J->n, rval);
-            } else if (!J->srows.active) {
-                long long g2 = std::min<long long>((J->nnz + LSQ_NT - 1) / LSQ_NT, (long long)c->num_cus * 16);
-                LSQ_LAUNCH(k_scale_csr, dim3((int)g2), dim3(LSQ_NT), 0, c->stream, J->nnz, J->csr.d_idx,
-                                   md->d_Acsr, md->d_s, J->csr.d_val);
-            } else {
-                // sliced rows without the LDS-staged scaling (forced onto a small pattern): rebuild from the CSC copy
-                if (lazy_csc) return 1;
-                if (lsq_mirror_rows(J, J->csc.d_val, rval) != LSQ_OK) return 1;
-            }
-        }
-        if (have_cols) {
-            if (lds_ok && ccol) {
-                LSQ_LAUNCH(k_scale_lds<false>, dim3(c->num_cus), dim3(1024), lds, c->stream, (clen + 3) / 4,
-                                   ccol, md->d_Ab, md->d_s, J->n, cval);
-            } else if (J->scols.active) {
-                // no LDS-staged scaling: rebuild the sliced columns from the CSC copy instead
-                if (lazy_csc) return 1;
-                if (lsq_mirror_cols(J, J->csc.d_val, cval) != LSQ_OK) return 1;
-            } else if (J->nnz < 16LL * J->bcsc.nseg) {
-                int nsegs = J->bcsc.nseg;
-                int g3 = std::min(lsq_div_up(nsegs, LSQ_NT), c->num_cus * 16);
-                LSQ_LAUNCH(k_scale_bcsc_thread, dim3(g3), dim3(LSQ_NT), 0, c->stream, nsegs, J->n,
-                                   J->bcsc.d_ptr, md->d_Ab, md->d_s, J->bcsc.d_val);
-            } else {
-                int nsegs = J->bcsc.nseg;
-                int g3 = std::min(lsq_div_up(nsegs, LSQ_NT / 64), c->num_cus * 16);
-                LSQ_LAUNCH(k_scale_bcsc, dim3(g3), dim3(LSQ_NT), 0, c->stream, nsegs, J->n, J->bcsc.d_ptr,
-                                   md->d_Ab, md->d_s, J->bcsc.d_val);
-            }
-        }
-        J->csr_fresh = true;  // every mirror written directly: no permutation pass needed
-    } else {
-        // dense columns: every block takes a (column, row chunk) pair, so that a matrix with few columns still fills the chip
-        const long long tot = (long long)J->m * J->n;
-        const int chunks = std::max(1, (int)std::min<long long>((J->m + 4 * LSQ_NT - 1) / (4 * LSQ_NT),
-                                                               std::max<long long>(1, (long long)c->num_cus * 16 / std::max(1, J->n))));
-        if (tot > 0)
-            LSQ_LAUNCH(k_scale_dense, dim3(J->n, chunks), dim3(LSQ_NT), 0, c->stream, J->m, md->d_Acsc, x, J->d_dense);
-    }
-    J->version++;
-    return hipGetLastError() == hipSuccess ? 0 : 1;
-}
-
-extern "C" lsq_f_callback lsq_model_f(void) { return model_f; }
-extern "C" lsq_g_callback lsq_model_g(void) { return model_g; }
-
-extern "C" int lsq_model_tanh_create(lsq_ctx *c, lsq_mat *J, const double *hA, const double *hb, lsq_model **out) {
-    if (!c || !J || !hA || !hb || !out) return LSQ_EARG;
-    LSQ_HIP(hipSetDevice(c->device));
-    lsq_model *md = new lsq_model();
-    md->ctx = c;
-    md->J = J;
-    const size_t nb = (size_t)(J->n > 0 ? J->n : 1) * sizeof(double);
-    LSQ_HIP(hipMalloc(&md->d_b, (size_t)(J->m > 0 ? J->m : 1) * sizeof(double)));
-    LSQ_HIP(hipMemcpy(md->d_b, hb, (size_t)J->m * sizeof(double), hipMemcpyHostToDevice));
-    LSQ_HIP(hipMalloc(&md->d_t, nb));
-    LSQ_HIP(hipMalloc(&md->d_s, nb));
-    LSQ_HIP(hipMalloc(&md->d_sspec, nb));
-    if (lsq_colscale_fusable(J)) {
-        // J's own storage takes A (once, in every layout); from here on J = A diag(s) through the handle's column scale
-        LSQ_TRY(lsq_mat_set_values(J, hA));
-        LSQ_TRY(lsq_fill(c, J->n, 1.0, md->d_s));
-        LSQ_TRY(lsq_mat_set_colscale(J, md->d_s));
-        md->fused = true;
-        LSQ_HIP(hipStreamSynchronize(c->stream));
-        *out = md;
-        return LSQ_OK;
-    }
-    size_t vb = (size_t)(J->nnz + 8) * sizeof(double);
-    LSQ_HIP(hipMalloc(&md->d_Acsc, vb));
-    LSQ_ZERO(md->d_Acsc, 0, vb);
-    LSQ_HIP(hipMemcpy(md->d_Acsc, hA, (size_t)J->nnz * sizeof(double), hipMemcpyHostToDevice));
-    if (J->kind == LSQ_MAT_CSC) {
-        // A in the layouts the products of J read (same maps as J's own mirrors), permuted once
-        const size_t rb = (size_t)(lsq_mirror_rows_len(J) + 1024) * sizeof(double);
-        LSQ_HIP(hipMalloc(&md->d_Acsr, rb));
-        LSQ_ZERO(md->d_Acsr, 0, rb);
-        LSQ_TRY(lsq_mirror_rows(J, md->d_Acsc, md->d_Acsr));
-        if (lsq_mirror_cols_len(J) > 0) {
-            const size_t cbytes = (size_t)(lsq_mirror_cols_len(J) + 1024) * sizeof(double);
-            LSQ_HIP(hipMalloc(&md->d_Ab, cbytes));
-            LSQ_ZERO(md->d_Ab, 0, cbytes);
-            LSQ_TRY(lsq_mirror_cols(J, md->d_Acsc, md->d_Ab));
-        }
-        LSQ_HIP(hipStreamSynchronize(c->stream));
-    }
-    *out = md;
-    return LSQ_OK;
-}
-
-extern "C" int lsq_model_paths(const lsq_model *md, int *sliced_rows, int *sliced_cols, int *lsmr_path, long long *pair_tails) {
-    if (!md || !sliced_rows || !sliced_cols || !lsmr_path || !pair_tails) {
-        lsq_set_error("lsq_model_paths: null argument");
-        return LSQ_EARG;
-    }
-    const lsq_mat *J = md->J;
-    *sliced_rows = J->kind == LSQ_MAT_CSC && J->srows.active;
-    *sliced_cols = J->kind == LSQ_MAT_CSC && J->scols.active;
-    const LsqWorkspace *w = (const LsqWorkspace *)md->ctx->workspace;
-    *lsmr_path = w && w->J == J && w->solver ? w->solver->last_lsmr_path : 0;
-    *pair_tails = md->pair_tails;
-    return LSQ_OK;
-}
-
-extern "C" int lsq_model_destroy(lsq_model *md) {
-    if (!md) return LSQ_OK;
-    hipStreamSynchronize(md->ctx->stream);
-    if (md->fused && md->J) lsq_mat_set_colscale(md->J, nullptr);   // (the factor vector goes away with the model)
-    hipFree(md->d_Acsc); hipFree(md->d_Acsr); hipFree(md->d_Ab); hipFree(md->d_b); hipFree(md->d_t); hipFree(md->d_s); hipFree(md->d_sspec);
-    hipFree(md->d_b_perm); hipFree(md->d_perm[0]); hipFree(md->d_perm[1]);
-    delete md;
-    return LSQ_OK;
 }

@@ -12,7 +12,7 @@ Run it after a change to lsq_sell.h / lsq_spmv.h and after a compiler update (ne
 
     python tools/stream_heads_isa.py            # or: make -C leastsquaresoptim.jl_amd/csrc check-heads
 
-It compiles lsq_sparse.hip and lsq_optimize.hip for gfx950 with the Makefile's flags and --save-temps into temporary
+It compiles lsq_sparse.hip and lsq_model.hip for gfx950 with the Makefile's flags and --save-temps into temporary
 directories, prints one line per sliced kernel they instantiate (VGPRs, spilled, scratch bytes, copies, requests of the first
 batch ahead of the barrier) and exits 1 if a kernel that must have the head lacks one of the three.  What it cannot decide is left to the reader: whether a wait sits on
 the path between the first copy and the batch for a launch's FIRST block (later blocks of a workgroup's block loop do wait);
@@ -31,7 +31,7 @@ DMA, BATCH = "global_load_lds_dwordx4", "global_load_dwordx4"
 # kernels that must have the DMA head (mangled-name fragments); the other sliced kernels are listed for their registers only
 HEADS = ("11k_sell_colsILb0E", "11k_sell_colsILb1E", "11k_sell_rowsI17EpiResidualSqPerm")
 LISTED = ("k_sell_",)
-SOURCES = ("lsq_sparse.hip", "lsq_optimize.hip")     # between them every instance named in HEADS
+SOURCES = ("lsq_sparse.hip", "lsq_model.hip")        # between them every instance named in HEADS
 
 
 def compile_isa(hipcc, source):
