@@ -414,10 +414,31 @@ typedef struct {
 
 void lsq_options_default(lsq_options *opt);
 /* optimize!(LeastSquaresProblemAllocated; kwargs...) -- levenberg_marquardt.jl:39-144,
- * dogleg.jl:41-203.  d_x (n) and d_fcur (m) are updated in place like nls.x / nls.y. */
+ * dogleg.jl:41-203.  d_x (n) and d_fcur (m) are updated in place like nls.x / nls.y.
+ * g = NULL is the reference's default problem (types.jl:54-58): wherever the loop would call g! it takes the central-difference
+ * Jacobian of f on the device (lsq_fd_jacobian below, same handles, same bits).  f_calls counts the optimizer's own evaluations
+ * only (the reference's closure calls f! inside g! uncounted), g_calls as with a callback.  A handle lsq_fd_jacobian refuses:
+ * LSQ_EARG with the reason in lsq_last_error.  lsq_optimize_batched takes g = NULL the same way. */
 int lsq_optimize(lsq_ctx *ctx, int optimizer, int solver_kind, lsq_mat *J, double *d_x,
                  double *d_fcur, lsq_f_callback f, lsq_g_callback g, void *user,
                  const lsq_options *opt, lsq_result *res);
+/* The Jacobian of f at d_x by central differences, on the device, written into lsq_mat_values(J) and followed by what the
+ * loops do after a g! callback (lsq_mat_refresh: every layout of the handle sees the new values).  This is the g! of the
+ * reference's default problem, LeastSquaresProblem(x, y, f!) without g! (types.jl:54-58).  d_x: n doubles, not written.
+ * The step of entry j is h = max(eps3 |x_j|, eps3) with eps3 = 0x1.965fea53d6e41p-18; x_j + h and x_j - h are formed from
+ * x_j, the column is (f(x+) - f(x-)) / (2 h), each operation correctly rounded: the bits a host loop in IEEE doubles gives.
+ * Columns that no residual row shares are perturbed in ONE pair of evaluations (a colour), and f always sees full vectors:
+ *   dense m x n (lsq_dense_create): n colours, one column each;
+ *   block-diagonal (lsq_blockdiag_create): nb colours -- colour c is column c of EVERY block, each with its own h -- so a
+ *     Jacobian costs 2 nb evaluations of f whatever the number of blocks is; f must be block-separable, as the handle says;
+ *   bordered (lsq_blockdiag_bordered_create): those nb colours, then one per shared column: 2 (nb + ng) evaluations.
+ * f is called as f(d_fplus, d_xplus, user), then f(d_fminus, d_xminus, user), colour by colour in that order; besides them
+ * the stream carries one launch per colour and one in front.  The scratch (two work copies of x, f+ and f-) belongs to the
+ * handle: allocated by the first call, freed by lsq_mat_destroy.  Stream-ordered; no host wait of its own.
+ * A non-zero return of f: LSQ_ECALLBACK (the handle stays usable; its values are then a mix of old and new columns).
+ * LSQ_EARG, with the reason in lsq_last_error: a plain CSC handle (a general sparse pattern needs a column colouring, which is
+ * not built), an operator handle, a handle with a column scale set (lsq_mat_set_colscale), a null argument. */
+int lsq_fd_jacobian(lsq_ctx *ctx, lsq_mat *J, const double *d_x, lsq_f_callback f, void *user);
 
 /* ---- B independent fits stacked on a block-diagonal Jacobian: one trust region PER BLOCK ----
  * For every block b of J = blkdiag(J_1 .. J_B) (lsq_blockdiag_create, nb <= 64) this runs the reference's optimize!
@@ -442,7 +463,9 @@ int lsq_optimize(lsq_ctx *ctx, int optimizer, int solver_kind, lsq_mat *J, doubl
  * called once per outer iteration for all blocks: g is handed, for every block that does not need a new Jacobian, the x_b at
  * which that block's Jacobian was last evaluated (the reference does not re-evaluate J_b at a reverted iterate,
  * levenberg_marquardt.jl:135), and the trial point holds a frozen block's final x_b; what f writes into the rows of frozen
- * blocks is ignored.  Refused with LSQ_EARG: a handle that is not block-diagonal, nb > 64, LSQ_QR, LSQ_LSMR, and any of
+ * blocks is ignored.  g = NULL: central differences of f (lsq_fd_jacobian) at those same per-block points, every block rewritten --
+ * a block that did not want its Jacobian gets the bits it already holds; its 2 nb evaluations of f are not counted in f_calls.
+ * Refused with LSQ_EARG: a handle that is not block-diagonal, nb > 64, LSQ_QR, LSQ_LSMR, and any of
  * allreduce / row_allreduce / the preconditioner hooks in the options.
  * All arrays of the result are HOST arrays owned by the caller, of length B unless said otherwise; any may be NULL.  The
  * trace (trace_cap > 0 and all six trace pointers set): row k, 0-based, of block b -- [k * B + b], x: [k * n + b * nb ..] --

@@ -175,6 +175,7 @@ def lib():
                              C.POINTER(Result)]),
         "lsq_optimize_batched": (i, [vp, i, i, vp, vp, vp, F_CALLBACK, G_CALLBACK, vp, C.POINTER(Options),
                                      C.POINTER(BatchedResult)]),
+        "lsq_fd_jacobian": (i, [vp, vp, vp, F_CALLBACK, vp]),
         "lsq_model_tanh_create": (i, [vp, vp, c_dp, c_dp, pvp]),
         "lsq_model_destroy": (i, [vp]),
         "lsq_model_f": (F_CALLBACK, []),

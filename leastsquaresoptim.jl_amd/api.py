@@ -999,8 +999,13 @@ class LeastSquaresProblem:
             raise DimensionMismatch(_lib.EDIM, "y must have length size(J, 1)")
         self.J = J
         self.f_ = f_
+        self._fd_g = None
         if g_ is None:
-            if autodiff == "central":
+            if autodiff == "central" and (_is_blockdiag(J) or _is_bordered(J)):
+                # the coloured host twin for the Python-level loops; optimize_ / optimize_batched_ / an allocated problem hand
+                # the native loops a NULL g! instead (central differences on the device) as long as g_ is still this one
+                g_ = self._fd_g = _colored_difference_jacobian(f_, len(self.y))
+            elif autodiff == "central":
                 g_ = _central_difference_jacobian(f_, len(self.y))
             elif autodiff == "forward":
                 raise NotImplementedError("autodiff=:forward (ForwardDiff) is off the hot path and "
@@ -1030,6 +1035,90 @@ def _central_difference_jacobian(f_, m):
             J[:, j] = (fp - fm) / (2 * h)
 
     return g_
+
+
+FD_EPS3 = float.fromhex("0x1.965fea53d6e41p-18")     # np.finfo(float).eps ** (1 / 3), the literal of csrc/lsq_fd.hip
+
+
+def _colored_difference_jacobian(f_, m):
+    """The same central differences on a BlockDiagonal / BorderedBlockDiagonal J, by COLOURS: column c of every block is
+    perturbed in one pair of evaluations (each entry with its own h), then every shared column on its own -- 2 nb (+ 2 ng)
+    calls of f_ whatever the number of blocks is.  The host twin of lsq_fd_jacobian: the same f_ calls in the same order on
+    the same full vectors, the same arithmetic per entry, so the same bits for the same f_."""
+    eps3 = FD_EPS3
+
+    def step(xj):   # max(eps3 * abs(xj), eps3) as Python's max evaluates it, elementwise
+        a = eps3 * np.abs(xj)
+        return np.where(eps3 > a, eps3, a)
+
+    def g_(J, x):
+        if not (_is_blockdiag(J) or _is_bordered(J)):
+            raise ArgumentError(_lib.EARG, "coloured central differences need a BlockDiagonal or BorderedBlockDiagonal Jacobian")
+        B, mb, nb, ng = J.nblocks, J.mb, J.nb, getattr(J, "ng", 0)
+        x0 = np.array(x, dtype=np.float64)
+        xp, xm = x0.copy(), x0.copy()
+        fp, fm = np.zeros(m), np.zeros(m)
+        blocks = J.data[:B * mb * nb].reshape(B, nb, mb)
+        for c in range(nb):
+            idx = np.arange(B) * nb + c
+            xj = x0[idx]
+            h = step(xj)
+            xp[idx] = xj + h
+            xm[idx] = xj - h
+            f_(fp, xp)
+            f_(fm, xm)
+            xp[idx] = xj
+            xm[idx] = xj
+            blocks[:, c, :] = (fp - fm).reshape(B, mb) / (2 * h)[:, None]
+        for k in range(ng):
+            j = B * nb + k
+            xj = x0[j]
+            h = float(step(xj))
+            xp[j] = xj + h
+            xm[j] = xj - h
+            f_(fp, xp)
+            f_(fm, xm)
+            xp[j] = xj
+            xm[j] = xj
+            J.data[B * mb * nb + k * m:B * mb * nb + (k + 1) * m] = (fp - fm) / (2 * h)
+
+    return g_
+
+
+def _device_fd(nls):
+    """Does this problem take its Jacobian from the device's central differences (g_ was left to the default on a block
+    handle, and is still that default)?"""
+    twin = getattr(nls, "_fd_g", None)
+    return twin is not None and nls.g_ is twin
+
+
+def fd_jacobian_(Jd, x, f_):
+    """lsq_fd_jacobian: the values of the DeviceMatrix Jd <- central differences of the host f_(out, x) at x (a DeviceVector,
+    or n host values), colour by colour on the device; every layout of the handle is refreshed.  Dense, block-diagonal and
+    bordered handles; anything else raises ArgumentError.  An exception raised by f_ is re-raised here."""
+    ctx = Jd.ctx
+    dx = x if hasattr(x, "ptr") else DeviceVector(ctx, Jd.n, x)
+    if dx.n != Jd.n:
+        raise DimensionMismatch(_lib.EDIM, "x has length %d, expected %d" % (dx.n, Jd.n))
+    xh, yh, err = np.zeros(Jd.n), np.zeros(Jd.m), []
+
+    def _fcb(d_out, d_x, _):
+        L = lib()
+        try:
+            check(L.lsq_d2h(ctx.h, xh.ctypes.data_as(C.c_void_p), d_x, Jd.n * 8))
+            f_(yh, xh)
+            check(L.lsq_h2d(ctx.h, d_out, yh.ctypes.data_as(C.c_void_p), Jd.m * 8))
+            return 0
+        except Exception as e:  # surfaced after the C call returns
+            err.append(e)
+            return 1
+
+    F = _lib.F_CALLBACK(_fcb)
+    st = lib().lsq_fd_jacobian(ctx.h, Jd.h, dx.ptr, F, None)
+    if err:
+        raise err[0]
+    check(st)
+    return Jd
 
 
 class LeastSquaresResult:
@@ -1065,6 +1154,9 @@ class _HostCallbacks:
 
     def __init__(self, ctx, nls, Jd, stage=None):
         self.ctx, self.nls, self.Jd = ctx, nls, Jd
+        # central differences on the device: the loop gets a NULL g! (.G), nothing is staged or uploaded, and the values are
+        # downloaded into nls.J.data once, at the end (fetch_jacobian)
+        self.device_fd = _device_fd(nls)
         self.n, self.m = len(nls.x), len(nls.y)
         self.is_op = isinstance(nls.J, DeviceOperator)
         self.own_stage = stage is None
@@ -1075,11 +1167,12 @@ class _HostCallbacks:
         self.J_for_g = None
         self.err = []
         self.xh, self.yh = np.zeros(self.n), np.zeros(self.m)
-        self.F, self.G = _lib.F_CALLBACK(self._fcb), _lib.G_CALLBACK(self._gcb)
+        self.F = _lib.F_CALLBACK(self._fcb)
+        self.G = _lib.G_CALLBACK() if self.device_fd else _lib.G_CALLBACK(self._gcb)
 
     def bind(self):
         # (called inside the caller's try: whatever happens after the rebinding, release() hands J.data back)
-        if self.is_op:
+        if self.is_op or self.device_fd:
             return
         nls, Jd = self.nls, self.Jd
         self.stage = self.given_stage if self.given_stage is not None else PinnedBuffer(self.ctx, Jd.nnz)
@@ -1121,6 +1214,11 @@ class _HostCallbacks:
         except Exception as e:
             self.err.append(e)
             return 1
+
+    def fetch_jacobian(self):
+        """device_fd: nls.J holds the Jacobian of the last evaluation (nothing was staged: release() has nothing to copy)."""
+        if self.device_fd:
+            self.nls.J.data[:] = self.Jd.values()
 
     def release(self):
         stage = self.stage
@@ -1257,6 +1355,7 @@ def optimize_(nls, optimizer=None, x_tol=1e-8, f_tol=1e-8, g_tol=1e-8, iteration
     finally:
         host.release()
         if st is not None:
+            host.fetch_jacobian()
             # optimize! mutates nls.x / nls.y in place (levenberg_marquardt.jl:46): when an iteration throws
             # (RankDeficientException, IsFiniteException, ...) they hold that iteration's iterate, as in the reference
             nls.x[:] = dx.get()
@@ -1446,6 +1545,7 @@ def optimize_batched_(nls, optimizer=None, x_tol=1e-8, f_tol=1e-8, g_tol=1e-8, i
     finally:
         host.release()
         if st is not None:
+            host.fetch_jacobian()
             nls.x[:] = dx.get()
             nls.y[:] = dy.get()
     if host.err:
@@ -1470,6 +1570,7 @@ class LeastSquaresProblemAllocated:
         self.solver = default_solver(optimizer.solver if optimizer is not None else None, nls.J)
         self.optimizer = default_optimizer(optimizer, self.solver, nls.J)
         self.x, self.y, self.f_, self.J, self.g_ = nls.x, nls.y, nls.f_, nls.J, nls.g_
+        self._fd_g = getattr(nls, "_fd_g", None)     # (g_ left to the default on a block handle: central differences on the device)
         self._Jd = nls.J if isinstance(nls.J, DeviceOperator) else DeviceMatrix(self.ctx, nls.J)
         self._dx = DeviceVector(self.ctx, len(nls.x), nls.x)
         self._dy = DeviceVector(self.ctx, len(nls.y), nls.y)

@@ -443,7 +443,7 @@ extern "C" int lsq_optimize_batched(lsq_ctx *c, int optimizer, int solver_kind, 
                                     lsq_f_callback f, lsq_g_callback g, void *user, const lsq_options *opt, void *result) {
     LSQ_RANGE("lsq_optimize_batched");
     lsq_batched_result *res = (lsq_batched_result *)result;
-    if (!c || !J || !x || !fcur || !f || !g || !opt || !res) {
+    if (!c || !J || !x || !fcur || !f || !opt || !res) {
         lsq_set_error("lsq_optimize_batched: null argument");
         return LSQ_EARG;
     }
@@ -491,6 +491,15 @@ extern "C" int lsq_optimize_batched(lsq_ctx *c, int optimizer, int solver_kind, 
         lsq_set_error("lsq_optimize_batched: preconditioner hooks belong to LSMR(); the per-block loop solves with Cholesky()");
         return LSQ_EARG;
     }
+    // g == NULL: g! is the central-difference Jacobian of f! (types.jl:54-58), nb colours whatever B is.  It is handed xg like
+    // any g! and rewrites every block: a block that did not want its Jacobian gets the bits it already holds
+    LsqFdCall fd{f, user, LSQ_OK};
+    if (!g) {
+        LSQ_TRY(lsq_fd_check(J, "lsq_optimize_batched without g!"));
+        f = lsq_fd_f_thunk;
+        g = lsq_fd_g_thunk;
+        user = &fd;
+    }
     LSQ_HIP(hipSetDevice(c->device));
     const int n = J->n;
     if (opt->h_lower || opt->h_upper) {        // levenberg_marquardt.jl:49-51 / dogleg.jl:52-54
@@ -503,9 +512,10 @@ extern "C" int lsq_optimize_batched(lsq_ctx *c, int optimizer, int solver_kind, 
             }
     }
     auto t0 = std::chrono::steady_clock::now();
-    const int st = optimizer == LSQ_LEVENBERG_MARQUARDT ? bt_loop<true>(c, J, qr, x, fcur, f, g, user, opt, res)
-                                                        : bt_loop<false>(c, J, qr, x, fcur, f, g, user, opt, res);
+    int st = optimizer == LSQ_LEVENBERG_MARQUARDT ? bt_loop<true>(c, J, qr, x, fcur, f, g, user, opt, res)
+                                                  : bt_loop<false>(c, J, qr, x, fcur, f, g, user, opt, res);
     hipStreamSynchronize(c->stream);
+    if (st == LSQ_ECALLBACK && fd.status != LSQ_OK) st = fd.status;    // (what the central differences themselves ran into)
     res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return st;
 }

@@ -285,6 +285,8 @@ struct lsq_mat {
     // dense columns of all m rows], nzval = the blocks as above, then the border column-major.  bd_* stay 0 on such a handle:
     // the shared columns couple the blocks, so nothing that works block by block may take it.  0 blocks: any other handle
     int br_blocks = 0, br_mb = 0, br_nb = 0, br_ng = 0;
+    // scratch of the central-difference Jacobian (lsq_fd.hip): x+ | x- | f+ | f-, allocated by the first lsq_fd_values
+    double *d_fd = nullptr;
 };
 
 // hipMemset runs on the NULL stream and is asynchronous to the host, while the library's stream is
@@ -496,5 +498,18 @@ int lsq_sparse_grad_colsum_spec(lsq_mat *J, const double *f, double *g, const do
 void lsq_sparse_grad_colsum_adopt(lsq_mat *J);   // the speculative pass ran for the handle's present factors: its colsumabs2 is current
 void lsq_sparse_colsum_forget(lsq_mat *J);       // ... or must not be trusted (it ran for factors that were never installed)
 const double *lsq_cached_colsum(lsq_mat *J);  // nullptr on failure (error set)
+// central-difference Jacobians (lsq_fd.hip).  lsq_fd_check: LSQ_EARG with the reason for a handle that has no colouring here;
+// lsq_fd_values: the stored values <- central differences of f at x (the caller refreshes the other layouts).  g == NULL in
+// lsq_optimize / lsq_optimize_batched: the loop runs on the two thunks with an LsqFdCall as their `user` -- its g! is
+// lsq_fd_values on the caller's f!, wherever the loop calls g!, and its f! is no longer the built-in model's to the loop
+struct LsqFdCall {
+    lsq_f_callback f;
+    void *user;
+    int status;     // of the last lsq_fd_values (a callback can only say "failed")
+};
+int lsq_fd_check(const lsq_mat *J, const char *who);
+int lsq_fd_values(lsq_mat *J, const double *x, lsq_f_callback f, void *user);
+int lsq_fd_f_thunk(double *d_out, const double *d_x, void *user);
+int lsq_fd_g_thunk(lsq_mat *J, const double *d_x, void *user);
 // reads slot values to host (synchronises the stream)
 int lsq_read_slots(lsq_ctx *ctx, int first, int count, double *h_out);

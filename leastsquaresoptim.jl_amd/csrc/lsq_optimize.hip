@@ -1092,12 +1092,24 @@ static int optimize_dogleg(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat *
 extern "C" int lsq_optimize(lsq_ctx *c, int optimizer, int solver_kind, lsq_mat *J, double *x, double *fcur,
                             lsq_f_callback f, lsq_g_callback g, void *user, const lsq_options *opt, lsq_result *res) {
     LSQ_RANGE("lsq_optimize");
-    if (!c || !J || !x || !fcur || !f || !g || !opt || !res) {
+    if (!c || !J || !x || !fcur || !f || !opt || !res) {
         lsq_set_error("lsq_optimize: null argument");
         return LSQ_EARG;
     }
     memset(res, 0, sizeof(*res));
     res->bad_index = -1;
+    // g == NULL: the reference's default problem (types.jl:54-58) -- g! is the central-difference Jacobian of f!, on the device
+    LsqFdCall fd{f, user, LSQ_OK};
+    if (!g) {
+        const int st0 = lsq_fd_check(J, "lsq_optimize without g!");
+        if (st0 != LSQ_OK) {
+            res->status = st0;
+            return st0;
+        }
+        f = lsq_fd_f_thunk;
+        g = lsq_fd_g_thunk;
+        user = &fd;
+    }
     LSQ_HIP(hipSetDevice(c->device));
     const int n = J->n;
     if (opt->h_lower || opt->h_upper) {
@@ -1164,6 +1176,7 @@ extern "C" int lsq_optimize(lsq_ctx *c, int optimizer, int solver_kind, lsq_mat 
     int st = lm ? optimize_lm(c, w->solver, *w->buf, J, x, fcur, f, g, user, opt, res)
                 : optimize_dogleg(c, w->solver, *w->buf, J, x, fcur, f, g, user, opt, res);
     hipStreamSynchronize(c->stream);
+    if (st == LSQ_ECALLBACK && fd.status != LSQ_OK) st = fd.status;    // (what the central differences themselves ran into)
     res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     res->status = st;
     return st;

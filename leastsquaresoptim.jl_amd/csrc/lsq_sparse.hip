@@ -551,6 +551,7 @@ extern "C" int lsq_mat_destroy(lsq_mat *J) {
     hipFree(J->d_colsum);
     hipFree(J->d_cs_base);
     hipFree(J->d_colsum_base);
+    hipFree(J->d_fd);
     delete J;
     return LSQ_OK;
 }
