@@ -431,14 +431,41 @@ int lsq_optimize(lsq_ctx *ctx, int optimizer, int solver_kind, lsq_mat *J, doubl
  *   dense m x n (lsq_dense_create): n colours, one column each;
  *   block-diagonal (lsq_blockdiag_create): nb colours -- colour c is column c of EVERY block, each with its own h -- so a
  *     Jacobian costs 2 nb evaluations of f whatever the number of blocks is; f must be block-separable, as the handle says;
- *   bordered (lsq_blockdiag_bordered_create): those nb colours, then one per shared column: 2 (nb + ng) evaluations.
+ *   bordered (lsq_blockdiag_bordered_create): those nb colours, then one per shared column: 2 (nb + ng) evaluations;
+ *   plain CSC (lsq_csc_create): the colouring attached with lsq_mat_set_fd_colouring below, 2 ncolours evaluations.
  * f is called as f(d_fplus, d_xplus, user), then f(d_fminus, d_xminus, user), colour by colour in that order; besides them
  * the stream carries one launch per colour and one in front.  The scratch (two work copies of x, f+ and f-) belongs to the
  * handle: allocated by the first call, freed by lsq_mat_destroy.  Stream-ordered; no host wait of its own.
  * A non-zero return of f: LSQ_ECALLBACK (the handle stays usable; its values are then a mix of old and new columns).
- * LSQ_EARG, with the reason in lsq_last_error: a plain CSC handle (a general sparse pattern needs a column colouring, which is
- * not built), an operator handle, a handle with a column scale set (lsq_mat_set_colscale), a null argument. */
+ * LSQ_EARG, with the reason in lsq_last_error: a plain CSC handle without a colouring (a general sparse pattern needs a column
+ * colouring: lsq_mat_set_fd_colouring), an operator handle, a handle with a column scale set (lsq_mat_set_colscale), a null
+ * argument. */
 int lsq_fd_jacobian(lsq_ctx *ctx, lsq_mat *J, const double *d_x, lsq_f_callback f, void *user);
+
+/* ---- central differences on a general sparse pattern: column colourings ----
+ * A colouring gives every column a colour 0 .. ncolours-1 so that the columns of one colour can be perturbed in one pair of
+ * evaluations of f.  It is VALID when no row of the pattern holds two columns of one colour; the largest number of entries in
+ * a row is therefore a lower bound on the number of colours of any valid colouring.
+ * lsq_csc_greedy_colouring (host arrays only, no context): first fit in natural column order -- colour[j] is the smallest
+ * c >= 0 that no column k < j sharing a row with j holds, an empty column gets 0.  Deterministic; sum over the rows of
+ * (entries of the row)^2 steps, O(n + nnz) memory.  h_colour: n ints, h_ncolours: one.  The pattern errors of lsq_csc_create
+ * (LSQ_EDIM / LSQ_EARG). */
+int lsq_csc_greedy_colouring(int m, int n, const int *h_colptr, const int *h_rowval, int *h_colour, int *h_ncolours);
+/* Attach a colouring to a plain CSC handle (lsq_csc_create): from then on lsq_fd_jacobian and g = NULL in lsq_optimize take
+ * it (every solver the handle takes).  h_colour_or_null: n host ints, NULL = the greedy colouring of the handle's own pattern;
+ * *h_ncolours (may be NULL) receives the number of colours.  A given array is checked in O(nnz + n): every value >= 0, every
+ * value 0 .. max used at least once, no row with two columns of one colour (the message names the row and the two columns);
+ * else LSQ_EARG and the handle keeps what it had.  Dense, block-diagonal and bordered handles have their built-in colouring
+ * and an operator has no values: LSQ_EARG with the reason.  A second call replaces the first; the tables (O(n) on the host
+ * and on the device) belong to the handle and go with lsq_mat_destroy; uploads of values, lsq_mat_refresh and
+ * lsq_mat_set_colscale leave them alone (a column scale is refused by lsq_fd_jacobian as on any handle).
+ * THE CONTRACT: the pattern must contain every (row, column) on which f depends.  A dependence that has no entry is not
+ * detected: it silently corrupts the other columns of that colour in that row.  An entry f does not depend on receives 0.
+ * The stream per Jacobian is as above: one launch in front, then per colour f, f and one launch, which writes every stored
+ * entry of the colour exactly once (balanced by stored entries, not by columns); about 28 bytes per stored entry in all. */
+int lsq_mat_set_fd_colouring(lsq_mat *J, const int *h_colour_or_null, int *h_ncolours);
+/* The attached colouring: *h_ncolours = 0 when none is attached; h_colour (n ints, may be NULL) is written otherwise. */
+int lsq_mat_fd_colouring(const lsq_mat *J, int *h_colour, int *h_ncolours);
 
 /* ---- B independent fits stacked on a block-diagonal Jacobian: one trust region PER BLOCK ----
  * For every block b of J = blkdiag(J_1 .. J_B) (lsq_blockdiag_create, nb <= 64) this runs the reference's optimize!

@@ -176,6 +176,9 @@ def lib():
         "lsq_optimize_batched": (i, [vp, i, i, vp, vp, vp, F_CALLBACK, G_CALLBACK, vp, C.POINTER(Options),
                                      C.POINTER(BatchedResult)]),
         "lsq_fd_jacobian": (i, [vp, vp, vp, F_CALLBACK, vp]),
+        "lsq_csc_greedy_colouring": (i, [i, i, c_ip, c_ip, c_ip, c_ip]),
+        "lsq_mat_set_fd_colouring": (i, [vp, c_ip, c_ip]),
+        "lsq_mat_fd_colouring": (i, [vp, c_ip, c_ip]),
         "lsq_model_tanh_create": (i, [vp, vp, c_dp, c_dp, pvp]),
         "lsq_model_destroy": (i, [vp]),
         "lsq_model_f": (F_CALLBACK, []),

@@ -567,6 +567,31 @@ class DeviceMatrix:
     def colscale_changed(self):
         check(lib().lsq_mat_colscale_changed(self.h))
 
+    def set_fd_colouring(self, colours=None):
+        """lsq_mat_set_fd_colouring: attach a column colouring to a plain CSC handle, after which fd_jacobian_ and the loops
+        with a NULL g! take central differences on it.  None: the greedy colouring of the handle's own pattern; else n colours
+        0 .. ncolours-1 (validated by the library: ArgumentError).  Returns the number of colours; a second call replaces
+        the first."""
+        ptr = None
+        if colours is not None:
+            a = np.ascontiguousarray(colours, dtype=np.int32)
+            if a.ndim != 1 or a.size != self.n:
+                raise ArgumentError(_lib.EARG, "a colouring has one colour per column: expected %d, got %d" % (self.n, a.size))
+            ptr = a.ctypes.data_as(_lib.c_ip)
+        nc = C.c_int(0)
+        check(lib().lsq_mat_set_fd_colouring(self.h, ptr, C.byref(nc)))
+        return nc.value
+
+    def fd_colouring(self):
+        """lsq_mat_fd_colouring: (int32 array of n colours, ncolours); (None, 0) when no colouring is attached."""
+        nc = C.c_int(0)
+        check(lib().lsq_mat_fd_colouring(self.h, None, C.byref(nc)))
+        if nc.value == 0:
+            return None, 0
+        out = np.zeros(self.n, dtype=np.int32)
+        check(lib().lsq_mat_fd_colouring(self.h, out.ctypes.data_as(_lib.c_ip), C.byref(nc)))
+        return out, nc.value
+
     def free(self):
         if self.h:
             lib().lsq_mat_destroy(self.h)
@@ -966,9 +991,11 @@ class OptimizationState:
 
 class LeastSquaresProblem:
     """types.jl:7-68.  J may be a numpy matrix (dense) or a scipy.sparse CSC matrix with a FIXED
-    pattern whose `.data` g_ overwrites (test/nonlinearleastsquares.jl:47-86)."""
+    pattern whose `.data` g_ overwrites (test/nonlinearleastsquares.jl:47-86).
+    autodiff="central_coloured" with a scipy.sparse J and no g_: coloured central differences on J's pattern, which must hold
+    every (row, column) f_ depends on; `colouring` is one colour per column (validated: ArgumentError), None the greedy one."""
 
-    def __init__(self, x=None, y=None, f_=None, g_=None, J=None, output_length=0, autodiff="central"):
+    def __init__(self, x=None, y=None, f_=None, g_=None, J=None, output_length=0, autodiff="central", colouring=None):
         if x is None:
             raise ValueError("initial x required")
         if f_ is None:
@@ -1000,8 +1027,21 @@ class LeastSquaresProblem:
         self.J = J
         self.f_ = f_
         self._fd_g = None
+        self._fd_colouring = None
         if g_ is None:
-            if autodiff == "central" and (_is_blockdiag(J) or _is_bordered(J)):
+            if autodiff == "central_coloured":
+                if not _is_sparse(J):
+                    raise ArgumentError(_lib.EARG, 'autodiff="central_coloured" needs a scipy.sparse J: its pattern is what is '
+                                                   'coloured (dense and block Jacobians take autodiff="central")')
+                if colouring is None:
+                    colouring = greedy_colouring(J)[0]
+                else:
+                    colouring = _check_colouring(J, colouring)
+                # as on block handles: the host twin for the Python-level loops; the native loops get a NULL g! and the
+                # colouring is attached to the DeviceMatrix, as long as g_ is still this one
+                self._fd_colouring = colouring
+                g_ = self._fd_g = _sparse_colored_difference_jacobian(f_, len(self.y), colouring)
+            elif autodiff == "central" and (_is_blockdiag(J) or _is_bordered(J)):
                 # the coloured host twin for the Python-level loops; optimize_ / optimize_batched_ / an allocated problem hand
                 # the native loops a NULL g! instead (central differences on the device) as long as g_ is still this one
                 g_ = self._fd_g = _colored_difference_jacobian(f_, len(self.y))
@@ -1085,9 +1125,126 @@ def _colored_difference_jacobian(f_, m):
     return g_
 
 
+def _csc_pattern(S):
+    """(m, n, colptr, rowval) of a scipy.sparse matrix in canonical CSC order, int32."""
+    S = S.tocsc()
+    if not S.has_sorted_indices:
+        S = S.sorted_indices()
+    m, n = S.shape
+    return m, n, np.ascontiguousarray(S.indptr, dtype=np.int32), np.ascontiguousarray(S.indices, dtype=np.int32)
+
+
+def greedy_colouring(S):
+    """lsq_csc_greedy_colouring on the pattern of the scipy.sparse S: (int32 array of n colours, ncolours).  First fit in
+    natural column order: colour[j] is the smallest c >= 0 that no column k < j sharing a row with j holds; no two columns of
+    one colour meet in a row, and the longest row is a lower bound on ncolours."""
+    m, n, colptr, rowval = _csc_pattern(S)
+    colour = np.zeros(n, dtype=np.int32)
+    nc = C.c_int(0)
+    check(lib().lsq_csc_greedy_colouring(m, n, colptr.ctypes.data_as(_lib.c_ip), rowval.ctypes.data_as(_lib.c_ip),
+                                         colour.ctypes.data_as(_lib.c_ip), C.byref(nc)))
+    return colour, nc.value
+
+
+def _greedy_colouring_host(S):
+    """The same algorithm in plain Python (the host twin of lsq_csc_greedy_colouring): stamp array over a row view."""
+    m, n, colptr, rowval = _csc_pattern(S)
+    R = _sp.csr_matrix((np.ones(len(rowval)), rowval, colptr), shape=(n, m)).tocsc()     # (the transpose's CSC = our CSR)
+    R.sort_indices()
+    rptr, ridx = R.indptr, R.indices
+    colour = np.zeros(n, dtype=np.int32)
+    stamp = np.full(n + 1, -1, dtype=np.int64)
+    nc = 0
+    for j in range(n):
+        for i in rowval[colptr[j]:colptr[j + 1]]:
+            for k in ridx[rptr[i]:rptr[i + 1]]:
+                if k >= j:
+                    break
+                stamp[colour[k]] = j
+        c = 0
+        while stamp[c] == j:
+            c += 1
+        colour[j] = c
+        nc = max(nc, c + 1)
+    return colour, nc
+
+
+def _check_colouring(S, colouring):
+    """What lsq_mat_set_fd_colouring checks, on the host: one colour >= 0 per column, every colour 0 .. max used, no row with
+    two columns of one colour.  Returns the colours as an int32 array; ArgumentError otherwise."""
+    m, n, colptr, rowval = _csc_pattern(S)
+    a = np.asarray(colouring)
+    if a.ndim != 1 or a.size != n or a.dtype.kind not in "iu":
+        raise ArgumentError(_lib.EARG, "a colouring has one integer colour per column (%d), got %r" % (n, a.shape))
+    a = a.astype(np.int64)
+    if n == 0:
+        return a.astype(np.int32)
+    if a.min() < 0:
+        j = int(np.argmin(a))
+        raise ArgumentError(_lib.EARG, "column %d has the negative colour %d" % (j, a[j]))
+    nc = int(a.max()) + 1
+    used = np.bincount(a, minlength=nc) if nc <= n else np.zeros(1)
+    if nc > n or np.any(used == 0):
+        raise ArgumentError(_lib.EARG, "the colours must be 0 .. ncolours-1 without a gap (largest colour %d)" % (nc - 1))
+    # (row, colour) of every stored entry: a valid colouring has no pair twice
+    col_of = np.repeat(np.arange(n), np.diff(colptr))
+    key = rowval.astype(np.int64) * nc + a[col_of]
+    order = np.argsort(key, kind="stable")
+    dup = np.flatnonzero((key[order][1:] == key[order][:-1]) & (col_of[order][1:] != col_of[order][:-1]))
+    if dup.size:
+        p, q = order[dup[0]], order[dup[0] + 1]
+        raise ArgumentError(_lib.EARG, "row %d holds columns %d and %d, both of colour %d" % (rowval[p], col_of[p], col_of[q],
+                                                                                             a[col_of[p]]))
+    return a.astype(np.int32)
+
+
+def _sparse_colored_difference_jacobian(f_, m, colour):
+    """Coloured central differences on a scipy.sparse J with a fixed pattern: all columns of one colour are perturbed in one
+    pair of evaluations (each with its own h), and every stored entry (i, j) is (f+[i] - f-[i]) / (2 h_j).  2 ncolours calls
+    of f_.  The host twin of lsq_fd_jacobian on a coloured CSC handle: the same f_ calls in the same order on the same full
+    vectors, the same arithmetic per entry, J.data written in canonical CSC order.  The pattern must hold every
+    (row, column) f_ depends on."""
+    eps3 = FD_EPS3
+    colour = np.asarray(colour, dtype=np.int64)
+    nc = int(colour.max()) + 1 if colour.size else 0
+    members = [np.flatnonzero(colour == c) for c in range(nc)]
+
+    def step(xj):   # max(eps3 * abs(xj), eps3) as Python's max evaluates it, elementwise
+        a = eps3 * np.abs(xj)
+        return np.where(eps3 > a, eps3, a)
+
+    def g_(J, x):
+        if not _is_sparse(J) or J.format != "csc":
+            raise ArgumentError(_lib.EARG, "coloured central differences on a pattern need a scipy.sparse CSC Jacobian")
+        if J.shape[1] != colour.size:
+            raise ArgumentError(_lib.EARG, "the colouring has %d columns, J has %d" % (colour.size, J.shape[1]))
+        colptr, rowval = J.indptr, J.indices
+        col_of = np.repeat(np.arange(J.shape[1]), np.diff(colptr))
+        x0 = np.array(x, dtype=np.float64)
+        xp, xm = x0.copy(), x0.copy()
+        fp, fm = np.zeros(m), np.zeros(m)
+        h_all = step(x0)
+        ecol = colour[col_of]                                  # the stored entries, grouped by the colour of their column
+        order = np.argsort(ecol, kind="stable")
+        cuts = np.searchsorted(ecol[order], np.arange(nc + 1))
+        for c, idx in enumerate(members):
+            xj = x0[idx]
+            h = h_all[idx]
+            xp[idx] = xj + h
+            xm[idx] = xj - h
+            f_(fp, xp)
+            f_(fm, xm)
+            xp[idx] = xj
+            xm[idx] = xj
+            ks = order[cuts[c]:cuts[c + 1]]
+            J.data[ks] = (fp[rowval[ks]] - fm[rowval[ks]]) / (2 * h_all[col_of[ks]])
+
+    return g_
+
+
 def _device_fd(nls):
     """Does this problem take its Jacobian from the device's central differences (g_ was left to the default on a block
-    handle, and is still that default)?"""
+    handle or to autodiff="central_coloured" on a sparse one, and is still that default)?"""
     twin = getattr(nls, "_fd_g", None)
     return twin is not None and nls.g_ is twin
 
@@ -1095,7 +1252,8 @@ def _device_fd(nls):
 def fd_jacobian_(Jd, x, f_):
     """lsq_fd_jacobian: the values of the DeviceMatrix Jd <- central differences of the host f_(out, x) at x (a DeviceVector,
     or n host values), colour by colour on the device; every layout of the handle is refreshed.  Dense, block-diagonal and
-    bordered handles; anything else raises ArgumentError.  An exception raised by f_ is re-raised here."""
+    bordered handles, and a sparse one with a colouring attached (DeviceMatrix.set_fd_colouring); anything else raises
+    ArgumentError.  An exception raised by f_ is re-raised here."""
     ctx = Jd.ctx
     dx = x if hasattr(x, "ptr") else DeviceVector(ctx, Jd.n, x)
     if dx.n != Jd.n:
@@ -1157,6 +1315,10 @@ class _HostCallbacks:
         # central differences on the device: the loop gets a NULL g! (.G), nothing is staged or uploaded, and the values are
         # downloaded into nls.J.data once, at the end (fetch_jacobian)
         self.device_fd = _device_fd(nls)
+        colouring = getattr(nls, "_fd_colouring", None)
+        if self.device_fd and colouring is not None and getattr(Jd, "_fd_attached", None) is not colouring:
+            Jd.set_fd_colouring(colouring)       # (a sparse J with autodiff="central_coloured"; once per handle)
+            Jd._fd_attached = colouring
         self.n, self.m = len(nls.x), len(nls.y)
         self.is_op = isinstance(nls.J, DeviceOperator)
         self.own_stage = stage is None
@@ -1571,6 +1733,7 @@ class LeastSquaresProblemAllocated:
         self.optimizer = default_optimizer(optimizer, self.solver, nls.J)
         self.x, self.y, self.f_, self.J, self.g_ = nls.x, nls.y, nls.f_, nls.J, nls.g_
         self._fd_g = getattr(nls, "_fd_g", None)     # (g_ left to the default on a block handle: central differences on the device)
+        self._fd_colouring = getattr(nls, "_fd_colouring", None)   # (or to "central_coloured" on a sparse one)
         self._Jd = nls.J if isinstance(nls.J, DeviceOperator) else DeviceMatrix(self.ctx, nls.J)
         self._dx = DeviceVector(self.ctx, len(nls.x), nls.x)
         self._dy = DeviceVector(self.ctx, len(nls.y), nls.y)
@@ -1586,13 +1749,15 @@ class LeastSquaresProblemAllocated:
             self._stage = None
 
 
-def optimize(f, x, optimizer, autodiff="central", **kwargs):
-    """optimize(f, x, optimizer; kwargs...) -- types.jl:182-184 (x is copied; f returns a vector)."""
+def optimize(f, x, optimizer, autodiff="central", J=None, colouring=None, **kwargs):
+    """optimize(f, x, optimizer; kwargs...) -- types.jl:182-184 (x is copied; f returns a vector).
+    autodiff="central_coloured" with J = a scipy.sparse pattern (and optionally a colouring): coloured central differences on
+    the device, as LeastSquaresProblem describes."""
     x0 = np.array(x, dtype=np.float64)
     out0 = np.atleast_1d(np.asarray(f(x0), dtype=np.float64))
 
     def f_(out, xx):
         out[:] = np.atleast_1d(f(xx))
 
-    nls = LeastSquaresProblem(x=x0.copy(), f_=f_, output_length=len(out0), autodiff=autodiff)
+    nls = LeastSquaresProblem(x=x0.copy(), f_=f_, J=J, output_length=len(out0), autodiff=autodiff, colouring=colouring)
     return optimize_(nls, optimizer, **kwargs)

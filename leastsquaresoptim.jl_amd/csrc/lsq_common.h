@@ -287,7 +287,23 @@ struct lsq_mat {
     int br_blocks = 0, br_mb = 0, br_nb = 0, br_ng = 0;
     // scratch of the central-difference Jacobian (lsq_fd.hip): x+ | x- | f+ | f-, allocated by the first lsq_fd_values
     double *d_fd = nullptr;
+    // column colouring of a plain CSC handle (lsq_mat_set_fd_colouring): nullptr = none attached.  Owned by the handle
+    struct LsqFdColouring *fdc = nullptr;
 };
+
+// A column colouring for central differences on a plain CSC handle (lsq_fd.hip).  Host: the colours as given, and per colour
+// where its columns (bound) and its stored entries (ebound) start in the colour-sorted order.  Device, O(n): the colours, the
+// columns sorted by colour (natural order inside one), and the running count of stored entries in that order.
+struct LsqFdColouring {
+    int ncolours = 0;
+    std::vector<int> colour;      // n
+    std::vector<int> bound;       // ncolours + 1: colour c is cols[bound[c] .. bound[c+1])
+    std::vector<int> ebound;      // ncolours + 1: off[bound[c]]
+    int *d_colour = nullptr;      // n
+    int *d_cols = nullptr;        // n
+    int *d_off = nullptr;         // n + 1
+};
+void lsq_fd_colouring_free(lsq_mat *J);
 
 // hipMemset runs on the NULL stream and is asynchronous to the host, while the library's stream is
 // non-blocking (not ordered against the NULL stream): a creation-time memset could therefore land

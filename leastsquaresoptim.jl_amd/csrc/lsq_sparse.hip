@@ -552,6 +552,7 @@ extern "C" int lsq_mat_destroy(lsq_mat *J) {
     hipFree(J->d_cs_base);
     hipFree(J->d_colsum_base);
     hipFree(J->d_fd);
+    lsq_fd_colouring_free(J);
     delete J;
     return LSQ_OK;
 }
