@@ -354,6 +354,10 @@ int lsq_ctx_device_info(const lsq_ctx *ctx, int *num_cus, int *num_xcds, char *a
  * enqueued behind the inner iteration at which the PREVIOUS solve stopped and skip themselves if this one is not over by then
  * (DESIGN 4.2).  h_out = {solves that were given such a guess, guesses that were wrong}; LSQ_NO_TAIL_SPECULATION=1 turns it off. */
 int lsq_ctx_tail_stats(const lsq_ctx *ctx, long long h_out[2]);
+/* Where the three-launch LSMR iteration expects the stop and its caller is the LM loop, one narrow launch (k_lsmr_commit_step)
+ * decides the iteration and, if the solve is over, takes the trust-region step as well.  h_out = {such launches that found the
+ * solve over, such launches that found it unfinished}; LSQ_NO_COMMIT_STEP=1 turns them off (cautious launches and k_step). */
+int lsq_ctx_commit_step_stats(const lsq_ctx *ctx, long long h_out[2]);
 
 /* ---- whole trust-region loop on device buffers (host control, device arrays) ---- */
 /* f!(out, x) and g!(J, x) on DEVICE pointers; g writes lsq_mat_values(J) (the library refreshes

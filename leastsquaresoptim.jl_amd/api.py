@@ -381,6 +381,13 @@ class Context:
         check(lib().lsq_ctx_tail_stats(self.h, v))
         return int(v[0]), int(v[1])
 
+    def commit_step_stats(self):
+        """lsq_ctx_commit_step_stats: k_lsmr_commit_step launches that (found their solve over and took the LM step, found it
+        unfinished)."""
+        v = (C.c_longlong * 2)()
+        check(lib().lsq_ctx_commit_step_stats(self.h, v))
+        return int(v[0]), int(v[1])
+
     def occupy(self, workgroups, lds_bytes=65536, milliseconds=10.0):
         """A neighbour on the device (lsq_bench_occupy): workgroups that hold LDS and spin, on a stream of their own."""
         check(lib().lsq_bench_occupy(self.h, int(workgroups), int(lds_bytes), float(milliseconds)))

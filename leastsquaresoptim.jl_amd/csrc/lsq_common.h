@@ -125,6 +125,8 @@ struct lsq_ctx {
     int fallback_giveups[4] = {0, 0, 0, 0};
     // LSMR solves whose caller's next kernels were enqueued behind a guessed last iteration (LsmrTail): {guesses, wrong ones}
     long long tail_spec[2] = {0, 0};
+    // k_lsmr_commit_step launches (lsq_lsmr3.h) that {found their solve over and took the step, found it unfinished}
+    long long commit_step[2] = {0, 0};
     hipStream_t occupy_stream = nullptr;   // lsq_bench_occupy
     // uploads that overlap compute (lsq_mat_set_values_async): created on first use
     hipStream_t copy_stream = nullptr;

@@ -809,6 +809,9 @@ static int lsmr_enqueue_setup(const LsmrWork &W, double *d_damp, const double *d
 // until it has reported (~8 us into it): if the solve is over the caller (lsq_lsmr_solve) queues the tail, unguarded, while the
 // cautious launch winds down; if not, the product of that launch is still streaming for 20 us and the next launches are queued
 // behind it as usual.  A wrong guess then costs a late product.
+// With the caller's step in hand (LsmrTail::step: the LM loop) that launch is k_lsmr_commit_step instead (lsq_lsmr3.h): ten
+// workgroups on C4, no product workgroups that stage w only to find `done`, and on a stop the step is taken inside it -- no
+// boundary, no k_step.  A wrong guess then costs that narrow launch and a host reaction in front of an ordinary launch.
 static int lsmr_run_fused(const LsmrWork &W, StopPredictor &pred, LsmrRun &r) {
     lsq_solver *s = W.s; lsq_ctx *c = W.c; lsq_mat *J = W.J;
     const LsmrTail *tail = W.tail;
@@ -826,10 +829,17 @@ static int lsmr_run_fused(const LsmrWork &W, StopPredictor &pred, LsmrRun &r) {
     const int pb = std::max(1, std::min(S.nblocks, c->num_cus - ub));
     int k1 = 0, enq = 0;         // K1' launches / whole iterations enqueued: k1 is enq or enq + 1
     const int test_no_record = getenv("LSQ_TEST_EXCHANGE_TIMEOUT") ? 1 : 0;       // (read once per solve, not per launch)
+    // The caller handed over its step: where a cautious launch would go, k_lsmr_commit_step decides iteration k1 instead -- and
+    // takes the step if the solve is over.  It is not a K1' launch: if it reports "not done" it has written nothing, and the
+    // ordinary launch k1 + 1 is queued as if it had never run (plain_j: never a second commit launch for the same iteration).
+    const bool commit_ok = W.spec && tail->step && tail->step_taken && !getenv("LSQ_NO_COMMIT_STEP");
+    bool commit_pending = false; // a commit launch is deciding iteration wait_at
+    int plain_j = 0;
+    unsigned fused_tag = 0u;     // the newest k_lsmr_fused launch's tag: the one a reader that gave up leaves behind
     LsmrProf prof{{c->prof_ev[0].size(), c->prof_ev[1].size()}, {}};
     unsigned long long spins = 0;
     // cautious: the product workgroups wait for the decision before they stream
-    auto launch_k1 = [&](bool cautious) -> int {
+    auto launch_k1 = [&](bool cautious, bool commit) -> int {
         const int j = k1 + 1, in = (j - 1) & 1, out = j & 1;
         LsmrFused a;
         a.st_in = W.stb[in]; a.st_out = W.stb[out]; a.mail = c->d_mail;
@@ -846,9 +856,15 @@ static int lsmr_run_fused(const LsmrWork &W, StopPredictor &pred, LsmrRun &r) {
         a.cautious = cautious ? 1 : 0;
         a.test_no_record = test_no_record;                      // (test hook: the in-launch hand-off fails)
         a.ho = W.fho;
-        a.tag_prev = j > 1 ? s->f3_tag : 0u;
+        a.tag_prev = j > 1 ? fused_tag : 0u;
         if (++s->f3_tag == 0u) s->f3_tag = 1u;                  // a counter per solver (= per record buffer): every older record
         a.tag = s->f3_tag;                                      // carries another value; 0 is the zeroed buffer
+        if (commit) {
+            LSQ_LAUNCH(k_lsmr_commit_step<0>, dim3(lsq_div_up(n, LSQ_BIG_NT)), dim3(LSQ_BIG_NT), 0, c->stream, a, *tail->step);
+            LSQ_HIP(hipGetLastError());
+            return LSQ_OK;
+        }
+        fused_tag = a.tag;
         if (c->prof_kernels & 1) lsq_prof_mark(c, 0, 0);
         hipEvent_t e0, e1;
         if (lsq_prof_take(c, &e0, &e1)) {
@@ -884,11 +900,16 @@ static int lsmr_run_fused(const LsmrWork &W, StopPredictor &pred, LsmrRun &r) {
         const unsigned long long w = lsmr_progress_word(c);
         const LsmrProgress p(w, W.epoch);
         if (r.see(p)) break;
-        if (wait_at > 0 && p.ours && r.it >= wait_at) {           // the cautious launch found the solve unfinished
+        if (wait_at > 0 && p.ours && r.it >= wait_at) {           // the cautious / commit launch found the solve unfinished
             if (wait_is_guess) {
                 c->tail_spec[0]++;
                 c->tail_spec[1]++;
                 planned = 0;
+            }
+            if (commit_pending) {
+                c->commit_step[1]++;
+                commit_pending = false;
+                plain_j = k1 + 1;
             }
             wait_at = 0;
         }
@@ -910,10 +931,16 @@ static int lsmr_run_fused(const LsmrWork &W, StopPredictor &pred, LsmrRun &r) {
                 // ... and also where nothing is known yet: the launch that decides iteration 1, unless the previous solve was a
                 // long one
                 const bool unknown = W.spec && enq == 1 && pred.hint_it == 0 && tail->predict <= 3;
-                LSQ_TRY(launch_k1(guess || unknown));
-                if (guess || unknown) {                          // nothing behind it until it has decided
-                    wait_at = enq;
-                    wait_is_guess = guess;
+                if (k1 + 1 == plain_j) {                         // (a commit launch has just reported this iteration unfinished)
+                    LSQ_TRY(launch_k1(false, false));
+                } else {
+                    const bool commit = commit_ok && (guess || unknown);
+                    LSQ_TRY(launch_k1(guess || unknown, commit));
+                    if (guess || unknown) {                      // nothing behind it until it has decided
+                        wait_at = enq;
+                        wait_is_guess = guess;
+                        commit_pending = commit;
+                    }
                 }
                 spins = 0;
                 continue;
@@ -921,15 +948,42 @@ static int lsmr_run_fused(const LsmrWork &W, StopPredictor &pred, LsmrRun &r) {
         }
         if (c->idle_hook) lsq_run_idle_hook(c);
         if ((++spins & 0x3ffu) != 0) continue;
-        LSQ_TRY(lsmr_stream_drained(c, W.epoch, k1 - 1, W.stb[k1 & 1], enq >= W.maxiter + 1, r));
+        // (a pending commit launch decides iteration k1 and, only if that ends the solve, leaves its state in set (k1 + 1) & 1)
+        const int newest = commit_pending ? k1 + 1 : k1;
+        LSQ_TRY(lsmr_stream_drained(c, W.epoch, newest - 1, W.stb[newest & 1], enq >= W.maxiter + 1, r));
+        if (commit_pending && !r.finished && r.it < wait_at && hipStreamQuery(c->stream) == hipSuccess) {
+            // (mailbox not visible, stream drained, no stop in that set: the commit launch found the solve unfinished)
+            const LsmrProgress q(lsmr_progress_word(c), W.epoch);
+            if (!(q.ours && (q.done || q.iter >= wait_at))) {
+                LsmrState hs;
+                LSQ_HIP(hipMemcpy(&hs, W.stb[k1 & 1], sizeof(hs), hipMemcpyDeviceToHost));
+                if (hs.done) { r.it = hs.iter; r.istop = hs.istop; r.finished = true; }
+                else {
+                    if (wait_is_guess) { c->tail_spec[0]++; c->tail_spec[1]++; planned = 0; }
+                    c->commit_step[1]++;
+                    commit_pending = false;
+                    plain_j = k1 + 1;
+                    wait_at = 0;
+                }
+            }
+        }
     }
     lsmr_drop_idle_samples(c, prof, r.it);
     if (r.istop == 99) {     // (a product workgroup gave up waiting for workgroup 0's record: lsq_lsmr3.h)
         lsq_set_error("lsmr: the in-launch hand-off of k_lsmr_fused timed out");
         return LSQ_EHIP;
     }
-    // a stop BEFORE wait_at (it < wait_at: an older launch committed it) is counted as a right guess here; to be fixed
-    if (wait_at > 0 && wait_is_guess) c->tail_spec[0]++;          // the predicted stop was the stop (a right guess)
+    // the launch that was to decide iteration wait_at is still the newest one: the stop is either that iteration's (a right guess)
+    // or an EARLIER one's, committed by an older launch while this one was in the queue (a wrong guess: it then found a finished
+    // solve, handed the state on and -- a commit launch -- took no step)
+    if (wait_at > 0 && wait_is_guess) {
+        c->tail_spec[0]++;
+        if (r.it < wait_at) c->tail_spec[1]++;
+    }
+    if (commit_pending && r.it >= wait_at) {
+        c->commit_step[0]++;
+        *tail->step_taken = true;
+    }
     return LSQ_OK;
 }
 
@@ -1029,6 +1083,7 @@ int lsq_lsmr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, double *d_damp,
                    const double *d_Jty, double y_sumsq, const LsmrLmPrep *lm, const LsmrTail *tail) {
     lsq_ctx *c = s->ctx;
     const int m = J->m, n = J->n;
+    if (tail && tail->step_taken) *tail->step_taken = false;      // (only lsmr_run_fused ever sets it)
     if (m != s->m || n != s->n) {
         lsq_set_error("lsmr: solver allocated for %dx%d, Jacobian is %dx%d", s->m, s->n, m, n);
         return LSQ_EDIM;

@@ -23,6 +23,8 @@
 // Where the host expects the launch to find the solve finished (lsmr_run_fused: the predicted last iteration; the first iteration
 // when nothing is known yet) it asks for a CAUTIOUS launch: the product workgroups wait for the record before they stream.  Every
 // launch is the whole grid: update workgroups in front, product workgroups behind them.
+// Where the caller is the LM loop and has handed over its step (LsmrTail::step), that launch is k_lsmr_commit_step instead (at
+// the end of this file): update work only, one element per thread, and on a stop the step x - P.*x as well.
 #pragma once
 
 constexpr int LSQ_FUSED_UB_MAX = 4;
@@ -177,6 +179,178 @@ __device__ __forceinline__ double lsq_block_reduce_lds(double v, double *sh /* 1
     return r;
 }
 
+// What K3 did (lsmr.jl:119-156, 205-231; iterative_lsmr.jl:92,195-196), for the workgroups of a launch that decide iteration j-1:
+// the update workgroups of k_lsmr_fused (STEP = false: NU groups of 1024 elements each, group blockIdx.x + k * gstride) and
+// every workgroup of k_lsmr_commit_step (STEP = true: one group each).  Both run the same expressions in the same order -- the
+// partials, the scalar chain, ||x|| over ALL of x, the rules, the state copy, the record, the progress word -- so which of the two
+// commits an iteration cannot show in a bit.
+// STEP: a launch that finds the solve UNFINISHED writes nothing a later launch reads (only the hints and the progress word: the
+// k_lsmr_fused launch behind it commits the iteration again from the same inputs); one that finds it finished also takes the
+// caller's step x - P.*x for its own elements (k_step of the LM loop: same expressions, both maxima through one ticket round).
+template <bool STEP, int NU>
+__device__ __forceinline__ void lsmr_update_groups(const LsmrFused &a, const LsmrStepDesc &sd, const int gstride, double *sh,
+                                                   LsmrState &ns) {
+    const int tid = threadIdx.x;
+    const int n = a.n;
+    static_assert(sizeof(LsmrState) % 8 == 0 && sizeof(LsmrState) / 8 <= LSQ_BIG_NT, "state copy: one 8-byte word per thread");
+    // These few workgroups run beside 250 streaming ones: a load takes microseconds, so every round of loads is issued as ONE
+    // batch.  Round 1: the state, the partials (inside ordered_sum256x3) and all of x, hbar, h for ||x||.
+    constexpr int NQ = (LSQ_LDS_X_MAX + LSQ_BIG_NT - 1) / LSQ_BIG_NT;
+    double xi[NQ], hbi[NQ], hi[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const int j = min(tid + q * LSQ_BIG_NT, n - 1);
+        xi[q] = a.x_in[j];
+        hbi[q] = a.hbar_in[j];
+        hi[q] = a.h_in[j];
+    }
+    if (tid < (int)(sizeof(LsmrState) / 8)) ((unsigned long long *)&ns)[tid] = ((const unsigned long long *)a.st_in)[tid];
+    // (did a product workgroup of the previous launch give up on its record?  every update workgroup looks, all decide alike)
+    const bool prev_failed = a.tag_prev != 0u &&
+                             (unsigned)__hip_atomic_load(&a.ho->w[6], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.tag_prev;
+    double beta2, betax2, alpha2;
+    ordered_sum512x3(a.pu_in, a.npu_in, a.px_in, a.npx_in, a.pv, a.npv, beta2, betax2, alpha2);   // (its barriers also publish ns)
+    if (ns.done) {    // a launch queued behind a finished solve: hand the state on (kernels behind it read st_out), release the readers
+        if (blockIdx.x == 0) {
+            if (tid < (int)(sizeof(LsmrState) / 8)) ((unsigned long long *)a.st_out)[tid] = ((const unsigned long long *)&ns)[tid];
+            if (tid == 0) {
+                lsmr_handoff_write(a.ho, a.tag, 1.0, 0.0, 1);
+                publish_relaxed(a.mail, &ns);      // (again: a failure mark of the previous launch's readers reaches the host this way)
+            }
+        }
+        return;       // (STEP: an older launch committed the stop -- its iteration number tells the host that no step was taken)
+    }
+    const bool was_first = ns.first != 0;
+    if (tid == 0) lsmr_scalars(ns, beta2, betax2, alpha2, a.dg != nullptr, a.px_in != nullptr);
+    __syncthreads();
+    if (!was_first) {
+        // ||x_k||^2 over ALL of x in every update workgroup alike (thread-strided, wave tree, 16 waves in order): no
+        // cross-workgroup reduction, the same bits everywhere
+        const double c1 = ns.c1, c2 = ns.c2;
+        double acc = 0.0;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const double hb = hbi[q] * c1 + hi[q];
+            const double xj = xi[q] + c2 * hb;
+            acc += (tid + q * LSQ_BIG_NT < n) ? xj * xj : 0.0;
+        }
+        const double total = block_sum<LSQ_BIG_NT>(acc, sh);
+        if (tid == 0) lsmr_decide(ns, total);
+    } else if (tid == 0) {
+        ns.first = 0;
+        if (!(ns.normAr != 0.0)) { ns.done = 1; ns.notdone = 0; }      // lsmr.jl:115: exit if b = 0 or A'b = 0
+    }
+    if (tid == 0 && prev_failed) { ns.istop = 99; ns.done = 1; ns.notdone = 0; }   // u~ of the previous launch is incomplete
+    __syncthreads();
+    const bool done_now = ns.done != 0;
+    const double vs = ns.vscale, cu = ns.cu, c1 = ns.c1, c2 = ns.c2, c3 = ns.c3;
+    if constexpr (STEP) {
+        if (!done_now) {    // the solve goes on: report it, leave set (j-1)&1 and everything else as it is
+            if (blockIdx.x == 0 && tid == 0) {
+                if (!was_first) {
+                    __hip_atomic_store((double *)&a.mail->test1, ns.normr / ns.normb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store((double *)&a.mail->test2, ns.normAr / (ns.normA * ns.normr), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                }
+                publish_relaxed(a.mail, &ns);
+            }
+            return;
+        }
+    }
+    if (blockIdx.x == 0) {
+        if (tid == 0 && !a.test_no_record) lsmr_handoff_write(a.ho, a.tag, vs, cu, done_now ? 1 : 0);   // first: somebody may be waiting for it
+        if (tid < (int)(sizeof(LsmrState) / 8)) ((unsigned long long *)a.st_out)[tid] = ((const unsigned long long *)&ns)[tid];
+        if (tid == 0) {
+            if (!was_first) {   // hints for the host's prediction of the stop iteration, in front of the progress word
+                __hip_atomic_store((double *)&a.mail->test1, ns.normr / ns.normb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                __hip_atomic_store((double *)&a.mail->test2, ns.normAr / (ns.normA * ns.normr), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+            publish_relaxed(a.mail, &ns);
+        }
+    }
+    // Round 2: this workgroup's own elements (every gstride-th group of 1024), again one batch of loads
+    double e_vt[NU], e_P[NU], e_dg[NU], e_ux[NU], e_h[NU], e_hb[NU], e_x[NU];
+    double e_s[NU];           // STEP: the caller's iterate
+#pragma unroll
+    for (int k = 0; k < NU; ++k) {
+        const int j = min((int)(blockIdx.x + k * gstride) * LSQ_BIG_NT + tid, n - 1);
+        e_vt[k] = a.vt[j];
+        e_P[k] = a.P ? a.P[j] : 1.0;
+        e_dg[k] = a.dg ? a.dg[j] : 0.0;
+        e_ux[k] = a.dg ? a.ux[j] : 0.0;
+        e_h[k] = a.h_in[j];
+        e_hb[k] = a.hbar_in[j];
+        e_x[k] = a.x_in[j];
+        if constexpr (STEP) e_s[k] = sd.x[j];
+    }
+    double aux = 0.0;
+    double mx = 0.0, code = 0.0;      // STEP: max|dx| and the first non-finite index of x_trial, as k_step codes them
+#pragma unroll
+    for (int k = 0; k < NU; ++k) {
+        const int j = (int)(blockIdx.x + k * gstride) * LSQ_BIG_NT + tid;
+        if (j >= n) continue;
+        const double Pj = e_P[k];
+        const double vj = e_vt[k] * vs;                 // lsmr.jl:78,124 rmul!(v, inv(alpha))
+        a.v[j] = vj;
+        double dj = 0.0;
+        if (was_first) {                                // :89-90, iterative_lsmr.jl:183,242
+            a.h_out[j] = vj;
+            a.hbar_out[j] = 0.0;
+            a.x_out[j] = 0.0;
+            a.xout[j] = 0.0;
+        } else {
+            const double hj = e_h[k];
+            const double hb = e_hb[k] * c1 + hj;        // :152-153
+            a.hbar_out[j] = hb;
+            const double xj = e_x[k] + c2 * hb;         // :154
+            a.x_out[j] = xj;
+            a.h_out[j] = hj * c3 + vj;                  // :155-156
+            dj = a.P ? xj * Pj : xj;                    // the caller's x always holds P.*x of the newest iterate
+            a.xout[j] = dj;
+        }
+        if constexpr (STEP) {     // k_step for element j, on the rounded P.*x that went to xout
+            const double v = e_s[k] + -1.0 * dj;        // axpy!(-1, dx, x)
+            sd.xt[j] = v;
+            if (sd.t_out) {
+                const double th = tanh(v);
+                sd.t_out[j] = th;
+                sd.s_out[j] = 1.0 - th * th;
+            }
+            double ad = fabs(dj);
+            if (isnan(ad)) ad = INFINITY;
+            mx = fmax(mx, ad);
+            if (!isfinite(v) && code == 0.0) code = 1e15 - (double)(j + 1);
+        }
+        if (a.dg && !done_now) {    // damped rows of the NEXT u (iterative_lsmr.jl:92): u~x <- d.*t - cu*u~x
+            const double tj = a.P ? vj * Pj : vj;       // iterative_lsmr.jl:31 ldiv!(tmp, P, a)
+            const double un = tj * e_dg[k] - cu * e_ux[k];
+            a.ux[j] = un;
+            aux += un * un;
+        }
+    }
+    if constexpr (STEP) {
+        // both maxima ride one ticket round across the grid, as in k_step: partials[b] and partials[LSQ_MAX_GRID + b] (maxima do
+        // not depend on the association, so the other grid shape cannot show)
+        const double b2 = lsq_block_reduce_lds<true>(code, sh);
+        if (tid == 0) __hip_atomic_store(&sd.partials[LSQ_MAX_GRID + blockIdx.x], b2, RLX_AGENT);
+        const double b1 = lsq_block_reduce_lds<true>(mx, sh);
+        const int nb = gridDim.x;
+        double *const out_dx = sd.out_dx;
+        if (grid_reduce<LSQ_BIG_NT, true>(b1, sd.partials, sd.counter, nb, sh, [=](double t) { *out_dx = t; })) {
+            double acc = 0.0;
+            for (int i = tid; i < nb; i += LSQ_BIG_NT) acc = fmax(acc, __hip_atomic_load(&sd.partials[LSQ_MAX_GRID + i], RLX_AGENT));
+            const double t = block_max<LSQ_BIG_NT>(acc, sh);
+            if (tid == 0) *sd.out_nonfin = (t == 0.0) ? -1.0 : (1e15 - t) - 1.0;
+        }
+        return;
+    }
+    if (done_now) return;        // (no next iteration: nobody reads sum(u~x^2))
+    const double bux = lsq_block_reduce_lds<false>(aux, sh);     // (block_sum's association: wave tree, 16 waves in order)
+    if (tid == 0) {
+        a.px_out[blockIdx.x] = bux;
+        if (blockIdx.x == 0) *a.npx_out = gstride;
+    }
+}
+
 template <int = 0>
 __global__ void __launch_bounds__(LSQ_BIG_NT) k_lsmr_fused(SellDev S, int wrows, int m, int nxpad, LsmrFused a) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -191,119 +365,8 @@ __global__ void __launch_bounds__(LSQ_BIG_NT) k_lsmr_fused(SellDev S, int wrows,
     const bool upd = (int)blockIdx.x < a.ub;   // update workgroups come first in the dispatch order: never queued behind a product
 
     if (upd) {
-        // ---- what K3 did (lsmr.jl:119-156, 205-231; iterative_lsmr.jl:92,195-196) ----
-        static_assert(sizeof(LsmrState) % 8 == 0 && sizeof(LsmrState) / 8 <= LSQ_BIG_NT, "state copy: one 8-byte word per thread");
-        // These few workgroups run beside 250 streaming ones: a load takes microseconds, so every round of loads is issued as ONE
-        // batch.  Round 1: the state, the partials (inside ordered_sum256x3) and all of x, hbar, h for ||x||.
         constexpr int NQ = (LSQ_LDS_X_MAX + LSQ_BIG_NT - 1) / LSQ_BIG_NT;
-        double xi[NQ], hbi[NQ], hi[NQ];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int j = min(tid + q * LSQ_BIG_NT, n - 1);
-            xi[q] = a.x_in[j];
-            hbi[q] = a.hbar_in[j];
-            hi[q] = a.h_in[j];
-        }
-        if (tid < (int)(sizeof(LsmrState) / 8)) ((unsigned long long *)&ns)[tid] = ((const unsigned long long *)a.st_in)[tid];
-        // (did a product workgroup of the previous launch give up on its record?  every update workgroup looks, all decide alike)
-        const bool prev_failed = a.tag_prev != 0u &&
-                                 (unsigned)__hip_atomic_load(&a.ho->w[6], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.tag_prev;
-        double beta2, betax2, alpha2;
-        ordered_sum512x3(a.pu_in, a.npu_in, a.px_in, a.npx_in, a.pv, a.npv, beta2, betax2, alpha2);   // (its barriers also publish ns)
-        if (ns.done) {    // a launch queued behind a finished solve: hand the state on (kernels behind it read st_out), release the readers
-            if (blockIdx.x == 0) {
-                if (tid < (int)(sizeof(LsmrState) / 8)) ((unsigned long long *)a.st_out)[tid] = ((const unsigned long long *)&ns)[tid];
-                if (tid == 0) {
-                    lsmr_handoff_write(a.ho, a.tag, 1.0, 0.0, 1);
-                    publish_relaxed(a.mail, &ns);      // (again: a failure mark of the previous launch's readers reaches the host this way)
-                }
-            }
-            return;
-        }
-        const bool was_first = ns.first != 0;
-        if (tid == 0) lsmr_scalars(ns, beta2, betax2, alpha2, a.dg != nullptr, a.px_in != nullptr);
-        __syncthreads();
-        if (!was_first) {
-            // ||x_k||^2 over ALL of x in every update workgroup alike (thread-strided, wave tree, 16 waves in order): no
-            // cross-workgroup reduction, the same bits everywhere
-            const double c1 = ns.c1, c2 = ns.c2;
-            double acc = 0.0;
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const double hb = hbi[q] * c1 + hi[q];
-                const double xj = xi[q] + c2 * hb;
-                acc += (tid + q * LSQ_BIG_NT < n) ? xj * xj : 0.0;
-            }
-            const double total = block_sum<LSQ_BIG_NT>(acc, sh);
-            if (tid == 0) lsmr_decide(ns, total);
-        } else if (tid == 0) {
-            ns.first = 0;
-            if (!(ns.normAr != 0.0)) { ns.done = 1; ns.notdone = 0; }      // lsmr.jl:115: exit if b = 0 or A'b = 0
-        }
-        if (tid == 0 && prev_failed) { ns.istop = 99; ns.done = 1; ns.notdone = 0; }   // u~ of the previous launch is incomplete
-        __syncthreads();
-        const bool done_now = ns.done != 0;
-        const double vs = ns.vscale, cu = ns.cu, c1 = ns.c1, c2 = ns.c2, c3 = ns.c3;
-        if (blockIdx.x == 0) {
-            if (tid == 0 && !a.test_no_record) lsmr_handoff_write(a.ho, a.tag, vs, cu, done_now ? 1 : 0);   // first: somebody may be waiting for it
-            if (tid < (int)(sizeof(LsmrState) / 8)) ((unsigned long long *)a.st_out)[tid] = ((const unsigned long long *)&ns)[tid];
-            if (tid == 0) {
-                if (!was_first) {   // hints for the host's prediction of the stop iteration, in front of the progress word
-                    __hip_atomic_store((double *)&a.mail->test1, ns.normr / ns.normb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    __hip_atomic_store((double *)&a.mail->test2, ns.normAr / (ns.normA * ns.normr), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
-                publish_relaxed(a.mail, &ns);
-            }
-        }
-        // Round 2: this workgroup's own elements (every ub-th group of 1024), again one batch of loads
-        constexpr int NU = (NQ + 2) / 3;      // ub >= 3
-        double e_vt[NU], e_P[NU], e_dg[NU], e_ux[NU], e_h[NU], e_hb[NU], e_x[NU];
-#pragma unroll
-        for (int k = 0; k < NU; ++k) {
-            const int j = min((int)(blockIdx.x + k * a.ub) * LSQ_BIG_NT + tid, n - 1);
-            e_vt[k] = a.vt[j];
-            e_P[k] = a.P ? a.P[j] : 1.0;
-            e_dg[k] = a.dg ? a.dg[j] : 0.0;
-            e_ux[k] = a.dg ? a.ux[j] : 0.0;
-            e_h[k] = a.h_in[j];
-            e_hb[k] = a.hbar_in[j];
-            e_x[k] = a.x_in[j];
-        }
-        double aux = 0.0;
-#pragma unroll
-        for (int k = 0; k < NU; ++k) {
-            const int j = (int)(blockIdx.x + k * a.ub) * LSQ_BIG_NT + tid;
-            if (j >= n) continue;
-            const double Pj = e_P[k];
-            const double vj = e_vt[k] * vs;                 // lsmr.jl:78,124 rmul!(v, inv(alpha))
-            a.v[j] = vj;
-            if (was_first) {                                // :89-90, iterative_lsmr.jl:183,242
-                a.h_out[j] = vj;
-                a.hbar_out[j] = 0.0;
-                a.x_out[j] = 0.0;
-                a.xout[j] = 0.0;
-            } else {
-                const double hj = e_h[k];
-                const double hb = e_hb[k] * c1 + hj;        // :152-153
-                a.hbar_out[j] = hb;
-                const double xj = e_x[k] + c2 * hb;         // :154
-                a.x_out[j] = xj;
-                a.h_out[j] = hj * c3 + vj;                  // :155-156
-                a.xout[j] = a.P ? xj * Pj : xj;             // the caller's x always holds P.*x of the newest iterate
-            }
-            if (a.dg && !done_now) {    // damped rows of the NEXT u (iterative_lsmr.jl:92): u~x <- d.*t - cu*u~x
-                const double tj = a.P ? vj * Pj : vj;       // iterative_lsmr.jl:31 ldiv!(tmp, P, a)
-                const double un = tj * e_dg[k] - cu * e_ux[k];
-                a.ux[j] = un;
-                aux += un * un;
-            }
-        }
-        if (done_now) return;        // (no next iteration: nobody reads sum(u~x^2))
-        const double bux = lsq_block_reduce_lds<false>(aux, sh);     // (block_sum's association: wave tree, 16 waves in order)
-        if (tid == 0) {
-            a.px_out[blockIdx.x] = bux;
-            if (blockIdx.x == 0) *a.npx_out = a.ub;
-        }
+        lsmr_update_groups<false, (NQ + 2) / 3>(a, LsmrStepDesc{}, a.ub, sh, ns);      // ub >= 3
         return;
     }
 
@@ -411,4 +474,19 @@ __global__ void __launch_bounds__(LSQ_BIG_NT) k_lsmr_fused(SellDev S, int wrows,
         a.pu_out[pb] = bv;
         if (pb == 0) *a.npu_out = npb;
     }
+}
+
+// The launch at which the host expects the stop (lsmr_run_fused, with a caller that handed over its step: LsmrStepDesc): as wide
+// as an n-length kernel should be -- ceil(n / 1024) workgroups, one element per thread --, no product workgroups, nothing queued
+// behind it.  It decides iteration j-1 exactly as the update workgroups of launch j would (lsmr_update_groups), from set (j-1)&1.
+//   * the solve is over: it commits what they would commit (x, h, hbar, v, the caller's P.*x, the state in set j&1, the record,
+//     the progress word) and takes the caller's step on the way: what a cautious k_lsmr_fused launch, a boundary and k_step did;
+//   * the solve goes on: it reports that and writes nothing else -- the ordinary k_lsmr_fused launch the host queues next commits
+//     the iteration again from the same, untouched inputs.  (sum(u~x^2) is reduced per update workgroup: partials of ANOTHER
+//     workgroup count would change its association, and with it the bits of the next beta.)
+template <int = 0>
+__global__ void __launch_bounds__(LSQ_BIG_NT) k_lsmr_commit_step(LsmrFused a, LsmrStepDesc sd) {
+    __shared__ double sh[LSQ_BIG_NT / 64];
+    __shared__ LsmrState ns;
+    lsmr_update_groups<true, 1>(a, sd, 0, sh, ns);
 }

@@ -692,11 +692,12 @@ struct LmTail {
     bool *spec_pending;     // (SpecGuard)
     LsqSlotPublish pub;     // out: the ticket the iteration's scalars arrive under
     bool spec_launched;     // out: of the LAST time the tail was queued (an earlier one skipped itself)
+    bool step_taken = false;    // the launch that committed the solve's stop has taken the step (LsmrTail::step_taken)
 };
 static int lm_tail(const int *skip, void *u) {
     LmTail &t = *(LmTail *)u;
     lsq_ctx *c = t.c;
-    LSQ_TRY(launch_step(c, t.is_model, t.user, t.gn, t.n, t.x, t.b->dx, t.xt, skip));   // :106
+    if (!t.step_taken) LSQ_TRY(launch_step(c, t.is_model, t.user, t.gn, t.n, t.x, t.b->dx, t.xt, skip));   // :106
     // the last kernel of the iteration hands the scalars to the host
     t.pub = lsq_slots_ticket(c, SL_GRAD, 6);      // (the sixth: whether the device let the queued pass run, k_sell_rows_pair)
     bool pair = false;
@@ -849,6 +850,13 @@ static int optimize_lm_loop(lsq_ctx *c, lsq_solver *sv, LoopBuffers &b, lsq_mat 
             static const bool no_spec = getenv("LSQ_NO_TAIL_SPECULATION") != nullptr;
             const bool guardable = tc.is_model && J->kind == LSQ_MAT_CSC && J->srows.active && !no_spec && !lsq_dbg_serial;
             LsmrTail tail{guardable ? last_inner : 0, lm_tail, &tc, guardable};
+            // the step as launch_step would queue it, for the launch that is expected to commit the stop (k_lsmr_commit_step)
+            LsmrStepDesc sd{x, xt, nullptr, nullptr, c->d_partials, lsq_ctr(c, 5), c->d_slots + SL_DX, c->d_slots + SL_NONFIN};
+            if (tail_ok && guardable) {
+                if (is_model) model_trial_buffers(user, xt, &sd.t_out, &sd.s_out);
+                tail.step = &sd;
+                tail.step_taken = &tc.step_taken;
+            }
             LSQ_TRY(lsq_lsmr_solve(sv, J, fcur, b.dtd, b.dx, &lmiter, b.grad, ssr, lm_prep ? &prep : nullptr,
                                    tail_ok ? &tail : nullptr));  // :87
             tail_done = tail_ok;

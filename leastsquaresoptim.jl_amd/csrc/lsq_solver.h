@@ -221,11 +221,26 @@ constexpr int LSMR_LM_PREP_MAX_N = 16384;   // every workgroup of that launch re
 // run the tail is called (again) with skip = nullptr after the solve.  predict == 0, general preconditioner, reference-order
 // kernels: called once after the solve.  `dynamic`: from inner iteration 1 on the guess is replaced by a prediction from the
 // hints beside the progress word (StopPredictor, lsq_lsmr.hip).
+// `step` (optional; plain device pointers): the tail BEGINS with the LM loop's step x_trial = x - d_x (k_step: with tanh and
+// 1 - tanh^2 of x_trial where t_out is set, max|d_x| -> *out_dx, the first non-finite index of x_trial -> *out_nonfin through one
+// ticket round on partials / counter).  The three-launch iteration then queues k_lsmr_commit_step (lsq_lsmr3.h) where it would
+// queue a cautious launch: if that launch finds the solve over it has taken the step itself and *step_taken is set before the
+// tail is called -- the tail then leaves its step kernel out.  A stop that an ordinary launch commits, every other driver and
+// LSQ_NO_COMMIT_STEP=1 leave *step_taken clear.
+struct LsmrStepDesc {
+    const double *x = nullptr;
+    double *xt = nullptr, *t_out = nullptr, *s_out = nullptr;
+    double *partials = nullptr;
+    unsigned *counter = nullptr;
+    double *out_dx = nullptr, *out_nonfin = nullptr;
+};
 struct LsmrTail {
     int predict = 0;
     int (*fn)(const int *skip, void *user) = nullptr;
     void *user = nullptr;
     bool dynamic = false;
+    const LsmrStepDesc *step = nullptr;
+    bool *step_taken = nullptr;
 };
 int lsq_rowshard_colsum(lsq_solver *s, lsq_mat *J, const double **out);   // colsumabs2 of the whole J (row-sharded: summed over the ranks)
 int lsq_lsmr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, double *d_damp, double *d_x, int *nmul,

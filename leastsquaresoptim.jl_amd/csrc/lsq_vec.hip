@@ -669,3 +669,9 @@ extern "C" int lsq_ctx_tail_stats(const lsq_ctx *c, long long h_out[2]) {
     h_out[1] = c->tail_spec[1];
     return LSQ_OK;
 }
+extern "C" int lsq_ctx_commit_step_stats(const lsq_ctx *c, long long h_out[2]) {
+    if (!c || !h_out) return LSQ_EARG;
+    h_out[0] = c->commit_step[0];
+    h_out[1] = c->commit_step[1];
+    return LSQ_OK;
+}
