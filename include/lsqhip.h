@@ -333,6 +333,36 @@ int lsq_dense_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double *d
  * is split into other slabs).  Waits where the solve waits (the certificate's copy) and once more, for the rank and s^2, which
  * are read back to back; the last two launches are stream-ordered behind that. */
 int lsq_dense_qr_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double *d_cov, double *d_stderr, int *h_info);
+/* G = J'J (+ diag(d_damp)) of a sparse Jacobian as a dense matrix, formed on the device without densifying J (k_sp_gram,
+ * lsq_cov_sparse.hip).  J: any LSQ_MAT_CSC handle -- lsq_csc_create, lsq_blockdiag_create, lsq_blockdiag_bordered_create -- at
+ * the values it holds; a column-scaled handle means J S.  d_damp: NULL or n doubles added to the diagonal.  d_G: n x n doubles,
+ * column-major: the upper triangle and the diagonal are written, the strict lower triangle is left alone.  Enqueues one kernel;
+ * stream-ordered, nothing is returned to the host.  Every entry is a sum over the rows that columns k and j share, taken in
+ * the order of column j's stored entries by one wavefront: no floating-point atomics, the same bits on every run and under
+ * lsq_debug_set; two columns that share no row give an exact 0.
+ * LSQ_EARG, each with a message in lsq_last_error: a dense handle, an operator handle, n > 16384 (one accumulator column of n
+ * doubles must fit the LDS of a workgroup).  n = 0: LSQ_OK, nothing is launched. */
+int lsq_sparse_gram(lsq_mat *J, const double *d_damp, double *d_G);
+/* lsq_dense_covariance, argument for argument, for a general sparse Jacobian: Cov = s^2 inv(J'J) without moving J to the host.
+ * J: an LSQ_MAT_CSC handle (plain, block-diagonal or bordered; for the latter two lsq_solver_covariance works block by block
+ * and has no limit on n); `s`: the LSQ_LSMR solver created on it, the one a sparse fit already owns.  The first call gives that
+ * solver an inner dense Cholesky() solver (n^2 doubles for J'J, 2 n^2 more for inv(U) and its workspace), freed with it.
+ *   d_f: NULL (the unscaled inv(J'J)) or the residual (m doubles, device): s^2 = sum(f.^2) / (m - n) through lsq_sumsq.
+ *   d_cov: NULL or n*n doubles, column-major, both triangles written with the same bits.  NULL allocates and writes no n x n
+ *   output: the standard errors alone are n doubles.
+ *   d_stderr: NULL or n doubles, from a kernel of their own with a fixed summation order: the same bits with and without d_cov.
+ * Launches, in stream order: lsq_sparse_gram's kernel into the inner solver, the factorisation of the dense damped solve with
+ * no damping added (one launch, or a launch per panel; the one-workgroup kernel where lsq_dense_covariance uses it), the
+ * explicit inverse of the factor, and the last two kernels of lsq_dense_covariance.  Waits for the stream once, in the middle,
+ * for the info word and s^2.  If the one-launch factorisation gives up on a wait, the Gram kernel and the panel launches run
+ * once more (lsq_solver_stats of `s`, index 0, counts it).  lsq_solver_chol_path of `s` afterwards reports 1, 2 or 4.
+ * A pivot that is not positive -- a structurally empty column among them: LSQ_ENOTPD, the 1-based column in the message and
+ * in h_info[0] when given (0 on success); the solver stays usable.  The result has the same bits on every run and under
+ * lsq_debug_set(serial = 1).
+ * LSQ_EARG, each with a message that names the alternative: a dense handle (lsq_dense_covariance), an operator handle, a
+ * solver that is not LSMR() or was created for another shape, a solver with a row all-reduce hook, d_cov and d_stderr both
+ * NULL, d_f with m <= n, n > 16384.  n = 0: LSQ_OK, nothing is launched. */
+int lsq_sparse_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double *d_cov, double *d_stderr, int *h_info);
 
 /* The fast paths above that rely on co-resident workgroups (one-launch Cholesky, pipelined triangular solves, the QR panel's slab
  * exchange + pipelined certified solve) wait with a bound; a wait that gives up makes the solve repeat itself on the

@@ -164,6 +164,8 @@ def lib():
         "lsq_solver_covariance": (i, [vp, vp, vp, vp, vp, c_ip]),
         "lsq_dense_covariance": (i, [vp, vp, vp, vp, vp, c_ip]),
         "lsq_dense_qr_covariance": (i, [vp, vp, vp, vp, vp, c_ip]),
+        "lsq_sparse_gram": (i, [vp, vp, vp]),
+        "lsq_sparse_covariance": (i, [vp, vp, vp, vp, vp, c_ip]),
         "lsq_solver_stats": (i, [vp, c_ip, c_ip]),
         "lsq_ctx_fallback_stats": (i, [vp, c_ip]),
         "lsq_ctx_device_info": (i, [vp, c_ip, c_ip, C.c_char_p, i]),

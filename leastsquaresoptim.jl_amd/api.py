@@ -888,6 +888,20 @@ class AllocatedSolver:
         check(lib().lsq_dense_qr_covariance(self.h, J.h, _ptr(df), dcov.ptr, _ptr(dse), info.ctypes.data_as(_lib.c_ip)))
         return DenseCovariance(J.n, dcov.get(), dse.get() if stderr else None)
 
+    def sparse_covariance(self, f=None, cov=True, stderr=True):
+        """lsq_sparse_covariance at the values the sparse (CSC) J holds now, on this LSMR() solver: a DenseCovariance with
+        `.chol_path`, the factorisation that ran on J'J.  `f` as for dense_covariance.  cov=False: the standard errors only --
+        no n x n output is allocated anywhere; `.cov` is then None."""
+        J = self.J
+        df = f if (f is None or hasattr(f, "ptr")) else DeviceVector(J.ctx, J.m, f)
+        n = J.n if (J.sparse and cov) else 0   # (any other handle is refused by the library, with its message)
+        dcov = DeviceVector(J.ctx, n * n) if cov else None
+        dse = DeviceVector(J.ctx, J.n) if stderr else None
+        info = np.zeros(1, dtype=np.int32)
+        check(lib().lsq_sparse_covariance(self.h, J.h, _ptr(df), _ptr(dcov), _ptr(dse), info.ctypes.data_as(_lib.c_ip)))
+        return DenseCovariance(J.n, dcov.get() if cov else None, dse.get() if stderr else None,
+                               chol_path=self.info()["chol_path"])
+
     def stats(self):
         """lsq_solver_stats: give-ups of the co-residency fast paths and how many solves each stays paused."""
         g, p = (C.c_int * 4)(), (C.c_int * 4)()
@@ -951,15 +965,20 @@ def covariance(Jd, f=None, stderr=True):
 
 class DenseCovariance:
     """What lsq_dense_covariance returns, on the host: `.cov` the n x n covariance s^2 inv(J'J) (symmetric to the bit),
-    `.stderr` the n standard errors (or None), `.n` the number of parameters."""
+    `.stderr` the n standard errors (or None), `.n` the number of parameters.  From lsq_sparse_covariance: `.cov` may be None
+    (cov=False), and `.chol_path` names the factorisation that ran on J'J (else None)."""
 
-    def __init__(self, n, cov, stderr=None):
+    def __init__(self, n, cov, stderr=None, chol_path=None):
         self.n = int(n)
-        cov = np.asarray(cov, dtype=np.float64)
-        if cov.size != self.n * self.n or cov.ndim > 2 or (cov.ndim == 2 and cov.shape != (self.n, self.n)):
-            raise DimensionMismatch(_lib.EDIM, "covariance of %d parameters has %d x %d entries, got %s"
-                                    % (self.n, self.n, self.n, cov.shape))
-        self.cov = cov.reshape((self.n, self.n), order="F")
+        self.chol_path = chol_path
+        if cov is None:
+            self.cov = None
+        else:
+            cov = np.asarray(cov, dtype=np.float64)
+            if cov.size != self.n * self.n or cov.ndim > 2 or (cov.ndim == 2 and cov.shape != (self.n, self.n)):
+                raise DimensionMismatch(_lib.EDIM, "covariance of %d parameters has %d x %d entries, got %s"
+                                        % (self.n, self.n, self.n, cov.shape))
+            self.cov = cov.reshape((self.n, self.n), order="F")
         self.stderr = None if stderr is None else np.asarray(stderr, dtype=np.float64)
         if self.stderr is not None and self.stderr.shape != (self.n,):
             raise DimensionMismatch(_lib.EDIM, "stderr has shape %s, expected %d values" % (self.stderr.shape, self.n))
@@ -983,6 +1002,28 @@ def dense_qr_covariance(Jd, f=None, stderr=True):
         return sv.dense_qr_covariance(f=f, stderr=stderr)
     finally:
         sv.free()
+
+
+def sparse_covariance(Jd, f=None, cov=True, stderr=True):
+    """Covariance of the parameters of a sparse (CSC) DeviceMatrix at the values it holds: creates an LSMR() solver on it, calls
+    AllocatedSolver.sparse_covariance and frees the solver."""
+    sv = AllocatedSolver(Jd, LSMR(), for_lm=True)
+    try:
+        return sv.sparse_covariance(f=f, cov=cov, stderr=stderr)
+    finally:
+        sv.free()
+
+
+def sparse_gram(Jd, damp=None):
+    """lsq_sparse_gram: J'J (+ diag(damp)) of a sparse (CSC) DeviceMatrix, formed on the device, as an n x n host array holding
+    the upper triangle (the strict lower triangle, which the kernel leaves alone, is zeroed here)."""
+    n = Jd.n if Jd.sparse else 0               # (any other handle is refused by the library, with its message)
+    dd = damp if (damp is None or hasattr(damp, "ptr")) else DeviceVector(Jd.ctx, Jd.n, damp)
+    dG = DeviceVector(Jd.ctx, n * n)
+    check(lib().lsq_sparse_gram(Jd.h, _ptr(dd), dG.ptr))
+    G = np.triu(dG.get().reshape((n, n), order="F"))
+    dG.free()
+    return G
 
 
 # ------------------------------------------------------------------------------------------------

@@ -157,6 +157,19 @@ static int factor_and_invert(lsq_solver *s, lsq_mat *J, bool allow_tiles) {
     return lsq_tri_inv_enqueue(s, s->d_chol, n);
 }
 
+// the last two launches on X = inv(U) in natural order: s2 X X' into d_cov, sqrt(s2) times the row norms of X into d_stderr,
+// whichever is given (also lsq_sparse_covariance, lsq_cov_sparse.hip)
+int lsq_cov_xxt_stderr(lsq_ctx *c, const double *X, int n, double s2, double *d_cov, double *d_stderr) {
+    if (d_cov) {
+        const int nt = lsq_div_up(n, CX_T);
+        LSQ_LAUNCH(k_cov_xxt<false>, dim3(nt * (nt + 1) / 2), dim3(256), 0, c->stream, X, n, s2, d_cov, (const int *)nullptr);
+    }
+    if (d_stderr) LSQ_LAUNCH(k_cov_stderr<false>, dim3(lsq_div_up(n, 4)), dim3(256), 0, c->stream, X, n, sqrt(s2), d_stderr,
+                                 (const int *)nullptr);
+    LSQ_HIP(hipGetLastError());
+    return LSQ_OK;
+}
+
 extern "C" int lsq_dense_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double *d_cov, double *d_stderr,
                                     int *h_info) {
     LSQ_RANGE("lsq_dense_covariance");
@@ -207,14 +220,7 @@ extern "C" int lsq_dense_covariance(lsq_solver *s, lsq_mat *J, const double *d_f
         return LSQ_ENOTPD;
     }
     const double s2 = d_f ? ssq / (double)(m - n) : 1.0;
-    if (d_cov) {
-        const int nt = lsq_div_up(n, CX_T);
-        LSQ_LAUNCH(k_cov_xxt<false>, dim3(nt * (nt + 1) / 2), dim3(256), 0, c->stream, (const double *)s->tri_X, n, s2, d_cov, (const int *)nullptr);
-    }
-    if (d_stderr) LSQ_LAUNCH(k_cov_stderr<false>, dim3(lsq_div_up(n, 4)), dim3(256), 0, c->stream, (const double *)s->tri_X, n, sqrt(s2), d_stderr,
-                                 (const int *)nullptr);
-    LSQ_HIP(hipGetLastError());
-    return LSQ_OK;
+    return lsq_cov_xxt_stderr(c, s->tri_X, n, s2, d_cov, d_stderr);
 }
 
 // ---------------------------------------------------------------------------------------------

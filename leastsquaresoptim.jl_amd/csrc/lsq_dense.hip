@@ -351,6 +351,12 @@ int lsq_cholesky_small_factor(lsq_solver *s, lsq_mat *J) {
     const int m = J->m, n = J->n;
     const int nt = (n + SY_T - 1) / SY_T;
     LSQ_LAUNCH(k_syrk_upper, dim3(nt * (nt + 1) / 2), dim3(256), 0, c->stream, J->d_dense, m, n, s->d_chol, (const double *)nullptr);
+    return lsq_cholesky_small_factor_ready(s, n);
+}
+
+// ... and its second half, on the G that stands in the upper triangle of s->d_chol (lsq_sparse_covariance behind k_sp_gram)
+int lsq_cholesky_small_factor_ready(lsq_solver *s, int n) {
+    lsq_ctx *c = s->ctx;
     LSQ_HIP(hipMemsetAsync(s->d_rhs, 0, (size_t)n * sizeof(double), c->stream));
     LSQ_LAUNCH((k_chol_solve<false>), dim3(1), dim3(CH_NT), 0, c->stream, s->d_chol, n, s->d_rhs, s->d_info, (int *)s->d_tau,
                s->d_work, s->d_work + 2 * n);

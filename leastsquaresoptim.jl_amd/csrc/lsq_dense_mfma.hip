@@ -833,6 +833,8 @@ k_diag_max(const double *__restrict__ C, int n, double *__restrict__ out) {
     if (threadIdx.x == 0) *out = v;
 }
 
+int lsq_cholesky_blocked_factor(lsq_solver *s, int n, double *d_x, bool allow_tiles);
+
 // dense_cholesky.jl:43-59: returns LSQ_ENOTPD through *info like the small kernel.  d_x == nullptr: factor only
 // (the caller decides about the solves); d_dmax != nullptr: also max_j (J'J + damp)_jj before the factorisation.
 // d_y: the right-hand side is J'y and d_x does not hold it yet (it is formed here, inside the SYRK launch where that applies)
@@ -876,6 +878,15 @@ int lsq_cholesky_blocked(lsq_solver *s, lsq_mat *J, const double *d_damp, double
         LSQ_LAUNCH(k_syrk_reduce, dim3(ntiles * 16), dim3(256), 0, c->stream, s->d_T, n, kslices, d_damp, s->d_chol, s->d_info);
     }
     if (d_dmax) LSQ_LAUNCH(k_diag_max, dim3(1), dim3(256), 0, c->stream, s->d_chol, n, d_dmax);
+    return lsq_cholesky_blocked_factor(s, n, d_x, allow_tiles);
+}
+
+// the factorisation (and, with d_x, the two triangular solves) on the G that stands in the upper triangle of s->d_chol, with
+// s->d_info[0] cleared by whoever wrote it: what lsq_cholesky_blocked enqueues behind its SYRK, and lsq_sparse_covariance
+// (lsq_cov_sparse.hip) behind k_sp_gram
+int lsq_cholesky_blocked_factor(lsq_solver *s, int n, double *d_x, bool allow_tiles) {
+    lsq_ctx *c = s->ctx;
+    const int nt = (n + MT - 1) / MT, ntiles = nt * (nt + 1) / 2;
     // one launch for the whole factorisation when the chain and every 64 x 64 upper tile get a CU of their own (k_chol_chain)
     if (allow_tiles && !s->fb_tiles.off() && ntiles + 1 <= c->num_cus && n >= 2 * NB && !getenv("LSQ_CHOL_PANELS")) {
         double *Xt = lsq_tri_chol_diagbuf(s, n);

@@ -135,6 +135,9 @@ struct lsq_solver {
     // bordered: zeros (the damping and right-hand side of the elimination) followed by the ng x ng block of the shared parameters
     int *d_cov_info = nullptr;
     double *d_cov_buf = nullptr;
+    // --- lsq_sparse_covariance on an LSMR() solver (lsq_cov_sparse.hip), created on first use: the dense Cholesky() solver
+    // (m, n of this one; lsq_dense_solver_alloc) whose d_chol receives J'J and which factors and inverts it
+    lsq_solver *cov_inner = nullptr;
 };
 int lsq_tri_chol_solve(lsq_solver *s, const double *U, int n, double *d_bx);
 int lsq_tri_chol_fwd_operands(lsq_solver *s, int n, double **z, unsigned long long **slot, unsigned long long *epoch, int **err);
@@ -259,6 +262,7 @@ int lsq_cholesky_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const doubl
 int lsq_qr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);
 bool lsq_cholesky_takes_blocked(int m, int n);
 int lsq_cholesky_small_factor(lsq_solver *s, lsq_mat *J);
+int lsq_cholesky_small_factor_ready(lsq_solver *s, int n);
 // implemented in lsq_qr.hip: X = inv(U) into the upper triangle of s->tri_X (stream-ordered; tri_X / tri_T allocated on first use)
 int lsq_tri_inv_enqueue(lsq_solver *s, const double *U, int n);
 // implemented in lsq_blockdiag.hip

@@ -42,6 +42,10 @@ extern "C" int lsq_solver_destroy(lsq_solver *s) {
     if (s->kind == LSQ_LSMR) lsq_lsmr_free(s);
     else lsq_dense_solver_free(s);     // (also the block-diagonal solvers: all they own is d_info, freed there)
     hipFree(s->d_cov_info); hipFree(s->d_cov_buf);     // lsq_solver_covariance
+    if (s->cov_inner) {                                // lsq_sparse_covariance
+        lsq_dense_solver_free(s->cov_inner);
+        delete s->cov_inner;
+    }
     delete s;
     return LSQ_OK;
 }
@@ -122,12 +126,16 @@ extern "C" int lsq_solver_stats(const lsq_solver *s, int h_giveups[4], int h_pau
         if (h_giveups) h_giveups[i] = fb[i]->giveups;
         if (h_paused) h_paused[i] = fb[i]->cooldown;
     }
+    if (s->cov_inner) {      // an LSMR() solver after lsq_sparse_covariance: the factorisation of its inner dense solver
+        if (h_giveups) h_giveups[0] += s->cov_inner->fb_tiles.giveups;
+        if (h_paused) h_paused[0] += s->cov_inner->fb_tiles.cooldown;
+    }
     return LSQ_OK;
 }
 
 extern "C" int lsq_solver_chol_path(const lsq_solver *s, int *path) {
     if (!s || !path) { lsq_set_error("lsq_solver_chol_path: null argument"); return LSQ_EARG; }
-    *path = s->last_chol_path;
+    *path = s->cov_inner ? s->cov_inner->last_chol_path : s->last_chol_path;   // (LSMR() after lsq_sparse_covariance: its factorisation)
     return LSQ_OK;
 }
 
