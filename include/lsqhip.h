@@ -37,8 +37,9 @@ typedef struct lsq_mat lsq_mat;       /* Jacobian: dense column-major or CSC (+C
 typedef struct lsq_solver lsq_solver; /* AbstractAllocatedSolver (types.jl:138-139) */
 typedef struct lsq_model lsq_model;   /* built-in device-side f!/g! (synthetic benchmarks) */
 
-/* types.jl:79-86; LSQ_BLOCK_QR: QR() per block of a block-diagonal handle (lsq_blockdiag_create), one rank decision per block */
-typedef enum { LSQ_QR = 0, LSQ_CHOLESKY = 1, LSQ_LSMR = 2, LSQ_BLOCK_QR = 3 } lsq_solver_kind;
+/* types.jl:79-86; LSQ_BLOCK_QR: QR() per block of a block-diagonal handle (lsq_blockdiag_create), one rank decision per block;
+ * LSQ_SCHUR: Cholesky()'s damped solve on a bordered handle (lsq_blockdiag_bordered_create) with any number of shared columns */
+typedef enum { LSQ_QR = 0, LSQ_CHOLESKY = 1, LSQ_LSMR = 2, LSQ_BLOCK_QR = 3, LSQ_SCHUR = 4 } lsq_solver_kind;
 typedef enum { LSQ_DOGLEG = 0, LSQ_LEVENBERG_MARQUARDT = 1 } lsq_optimizer_kind;   /* types.jl:90-98 */
 
 const char *lsq_last_error(void);
@@ -98,7 +99,21 @@ int lsq_mat_blockdiag_info(const lsq_mat *J, int *nblocks, int *mb, int *nb);
  * left as it is, a column-scaled handle means J S.  for_lm = 0 and lsq_ldiv (Dogleg(Cholesky())) are refused with LSQ_EARG on
  * purpose: the reference factors with diagonal pivoting over the whole stacked matrix (dense_cholesky.jl:29-35) and reports
  * RankDeficientException(rank) along that global pivot order, which does not split into "locals first".  LSQ_QR stays
- * refused.  Any of the four sizes < 1, or sizes past 32-bit indices: LSQ_EDIM. */
+ * refused.  Any of the four sizes < 1, or sizes past 32-bit indices: LSQ_EDIM.
+ * LSQ_SCHUR is the same solve without the limit on the border: lsq_solver_create accepts the handle with for_lm = 1 when
+ * nb <= 64, for ANY ng >= 1 (memory is the only cap: B*nb*ng doubles for the eliminated border rows, ng*ng for the Schur
+ * complement, and the split-K partials of two ng x ng products).  The locals are eliminated block by block in LDS, the border
+ * passes through in tiles of 64 columns, and the Schur complement S = C'C + D_g - W'W is factored by the dense Cholesky()
+ * machinery on an inner solver.  Semantics are those of LSQ_CHOLESKY on this handle, to the letter: the solution of
+ * (J'J + diag(damp)) x = J'y as unpivoted dpotrf on the stacked matrix with the locals first, nmul = 1, damp is not written, a
+ * column-scaled handle means J S, one trust region, LSQ_ENOTPD with the 1-based stacked column (b*nb + k in a local block,
+ * B*nb + k in the factor of S; the lowest wins) and the message "PosDefException: ... Cholesky failed at <column>"; the solver
+ * stays usable afterwards.  lsq_ldiv_damped and lsq_optimize with LSQ_LEVENBERG_MARQUARDT take it (g = NULL included);
+ * lsq_solver_blockdiag_path reports 5 (block as for 4), lsq_solver_chol_path the factorisation that took S (1, 2 or 4), and
+ * lsq_solver_stats index 0 counts a give-up of its one-launch form (S is then formed again and factored by panel launches).
+ * LSQ_EARG: any other handle (dense, plain CSC, block-diagonal, operator), nb > 64, for_lm = 0 / lsq_ldiv / Dogleg (the text
+ * of LSQ_CHOLESKY's refusal, for the same reason), lsq_optimize_batched, lsq_solver_covariance (lsq_sparse_covariance on an
+ * LSMR() solver serves the handle), a handle of another shape than the solver was created for. */
 int lsq_blockdiag_bordered_create(lsq_ctx *ctx, int nblocks, int mb, int nb, int ng, lsq_mat **out);
 /* all 0 for any other handle */
 int lsq_mat_bordered_info(const lsq_mat *J, int *nblocks, int *mb, int *nb, int *ng);
@@ -256,7 +271,7 @@ int lsq_solver_chol_path(const lsq_solver *s, int *path);
  * general preconditioner (lsq_lsmr_general.hip).  Read-only; the tests use it to know which copy of the stopping rules ran. */
 int lsq_solver_lsmr_path(const lsq_solver *s, int *path);
 /* diagnostics of the last block solve: which path (0 none yet, 1 batched unpivoted LM, 2 batched pivoted Dogleg, 3 batched
- * per-block pivoted QR: LSQ_BLOCK_QR, block = -1, 4 bordered Schur, LM: lsq_blockdiag_bordered_create) and, after LSQ_ENOTPD /
+ * per-block pivoted QR: LSQ_BLOCK_QR, block = -1, 4 bordered Schur, LM: lsq_blockdiag_bordered_create, 5 the same by LSQ_SCHUR) and, after LSQ_ENOTPD /
  * LSQ_ERANK, the block that decided it (path 4: nblocks when the Schur factor of the shared columns failed) (else -1) */
 int lsq_solver_blockdiag_path(const lsq_solver *s, int *path, int *block);
 /* LSQ_BLOCK_QR: the numerical rank of every block in the last solve (h_ranks: nblocks ints; -1 before the first solve).

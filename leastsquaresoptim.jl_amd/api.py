@@ -45,6 +45,14 @@ class BlockQR(AbstractSolver):
     kind = _lib.BLOCK_QR
 
 
+class Schur(AbstractSolver):
+    """Cholesky()'s damped solve on a BorderedBlockDiagonal Jacobian with ANY number of shared columns (nb <= 64;
+    LevenbergMarquardt only): the locals are eliminated block by block, the border passes through in tiles of 64 columns, and
+    the ng x ng Schur complement is factored by the dense Cholesky() machinery.  Same semantics as Cholesky() on that
+    container -- unpivoted dpotrf on the stacked normal matrix with the locals first, PosDefException at its column."""
+    kind = _lib.SCHUR
+
+
 class LSMR(AbstractSolver):
     """LSMR(preconditioner!, P) (types.jl:82-86).
 
@@ -207,7 +215,7 @@ class BorderedBlockDiagonal:
     to back, then the ng border columns of m values each.
     On the device it becomes a CSC handle that knows its shape (lsq_blockdiag_bordered_create): LSMR() is the default solver,
     Cholesky() eliminates the locals block by block and factors the ng x ng Schur complement (nb + ng <= 64;
-    LevenbergMarquardt only), QR() and BlockQR() are refused."""
+    LevenbergMarquardt only), Schur() does the same for any ng (nb <= 64), QR() and BlockQR() are refused."""
 
     def __init__(self, nblocks, mb, nb, ng, data=None):
         nblocks, mb, nb, ng = int(nblocks), int(mb), int(nb), int(ng)
@@ -290,6 +298,11 @@ BORDERED_DOGLEG_TEXT = ("Dogleg(Cholesky()) is not available on a bordered block
                         "Use LevenbergMarquardt(Cholesky()) or LSMR()")
 
 
+SCHUR_HANDLE_TEXT = ("Schur() needs a BorderedBlockDiagonal Jacobian (got a %s of shape %s). Use Cholesky() or QR() on a dense "
+                     "Jacobian, Cholesky() or BlockQR() on a BlockDiagonal one, LSMR() on a sparse one")
+SCHUR_NB_TEXT = "Schur() on a BorderedBlockDiagonal Jacobian needs nb <= 64 (got nb = %d, ng = %d). Use LSMR()"
+
+
 def _is_bordered(J):
     return isinstance(J, BorderedBlockDiagonal)
 
@@ -302,6 +315,12 @@ def default_solver(solver, J):
         return LSMR() if (_is_sparse(J) or _is_blockdiag(J) or _is_bordered(J) or matrix_free) else QR()
     if matrix_free and not isinstance(solver, LSMR):
         raise ArgumentError(_lib.EARG, "a matrix-free Jacobian works with LSMR() only (README.md:37-47)")
+    if isinstance(solver, Schur):
+        if not _is_bordered(J):
+            raise ArgumentError(_lib.EARG, SCHUR_HANDLE_TEXT % (type(J).__name__, tuple(getattr(J, "shape", ()))))
+        if J.nb > 64:
+            raise ArgumentError(_lib.EARG, SCHUR_NB_TEXT % (J.nb, J.ng))
+        return solver
     if _is_bordered(J):
         if isinstance(solver, QR):
             raise ArgumentError(_lib.EARG, "solver QR() is not available for a BorderedBlockDiagonal Jacobian. "
@@ -328,9 +347,9 @@ def default_solver(solver, J):
 
 
 def default_optimizer(optimizer, solver, J=None):
-    """types.jl:123-127.  On a BorderedBlockDiagonal J, Cholesky() comes with LevenbergMarquardt (Dogleg(Cholesky()) does not
-    exist there and is refused)."""
-    if _is_bordered(J) and isinstance(solver, Cholesky):
+    """types.jl:123-127.  On a BorderedBlockDiagonal J, Cholesky() and Schur() come with LevenbergMarquardt (Dogleg with either
+    does not exist there and is refused)."""
+    if isinstance(solver, Schur) or (_is_bordered(J) and isinstance(solver, Cholesky)):
         if isinstance(optimizer, Dogleg):
             raise ArgumentError(_lib.EARG, BORDERED_DOGLEG_TEXT)
         return LevenbergMarquardt(solver)
@@ -839,7 +858,7 @@ class AllocatedSolver:
             block_ranks = np.zeros(self.J.blockdiag_info()[0], dtype=np.int32)
             check(lib().lsq_solver_blockdiag_ranks(self.h, block_ranks.ctypes.data_as(_lib.c_ip)))
         return dict(blockdiag_path={0: None, 1: "batched-unpivoted", 2: "batched-pivoted", 3: "batched-qr",
-                                    4: "bordered-schur"}[bpath.value],
+                                    4: "bordered-schur", 5: "bordered-schur-tiled"}[bpath.value],
                     blockdiag_block=bblock.value, block_ranks=block_ranks,
                     lsmr_iter=it.value, lsmr_istop=st.value, qr_rank=rk.value,
                     lsmr_path={0: None, 1: "reference-order", 2: "four-launch", 3: "three-launch", 4: "general"}[lpath.value],
@@ -1674,6 +1693,10 @@ def _batched_arguments(J, optimizer, n, lower, upper):
     if isinstance(solver, QR):
         raise ArgumentError(_lib.EARG, "solver QR() is not available for sparse Jacobians. "
                                        "Choose between Cholesky() and LSMR()")
+    if isinstance(solver, Schur):
+        raise ArgumentError(_lib.EARG, "optimize_batched_: Schur() solves the one coupled system of a BorderedBlockDiagonal "
+                                       "Jacobian, there is no trust region per block in it. Use optimize_ with "
+                                       "LevenbergMarquardt(Schur())")
     if isinstance(solver, LSMR):
         raise ArgumentError(_lib.EARG, "optimize_batched_: LSMR() is not available per block (an iterative solve per block "
                                        "is a different loop). Use Cholesky(), or optimize_ for one trust region over the "

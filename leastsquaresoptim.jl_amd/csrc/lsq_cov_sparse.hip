@@ -4,7 +4,7 @@
 // Everything behind the Gram matrix is the dense covariance's (lsq_cov_dense.hip): the blocked Cholesky on a ready G
 // (lsq_cholesky_blocked_factor, lsq_dense_mfma.hip; the one-workgroup kernel for the few small operands the dense path keeps
 // away from it: lsq_cholesky_small_factor_ready, lsq_dense.hip), X = inv(U) (lsq_tri_inv_enqueue), k_cov_xxt and k_cov_stderr.
-// They run on an inner dense LSQ_CHOLESKY lsq_solver that the LSMR() solver of the fit creates on first use (lsq_solver::cov_inner).
+// They run on an inner dense LSQ_CHOLESKY lsq_solver that the LSMR() solver of the fit creates on first use (lsq_solver::inner).
 //
 // k_sp_gram: the upper triangle of G = J'J, column-major with leading dimension n, J never densified.
 //   One wavefront owns one output column j and a dense accumulator acc[0 .. n) of its own in LDS (zero between columns).  It
@@ -256,7 +256,7 @@ extern "C" int lsq_sparse_covariance(lsq_solver *s, lsq_mat *J, const double *d_
     if (n <= 0) return LSQ_OK;
     lsq_ctx *c = s->ctx;
     LSQ_HIP(hipSetDevice(c->device));
-    if (!s->cov_inner) {            // the dense Cholesky() solver behind the Gram matrix: n^2 doubles, more on first use
+    if (!s->inner) {            // the dense Cholesky() solver behind the Gram matrix: n^2 doubles, more on first use
         lsq_solver *in = new lsq_solver();
         in->ctx = c;
         in->kind = LSQ_CHOLESKY;
@@ -269,9 +269,9 @@ extern "C" int lsq_sparse_covariance(lsq_solver *s, lsq_mat *J, const double *d_
             delete in;
             return st;
         }
-        s->cov_inner = in;
+        s->inner = in;
     }
-    lsq_solver *in = s->cov_inner;
+    lsq_solver *in = s->inner;
     double ssq = 0.0;
     int st4[4] = {0, 0, 0, 0};
     for (int attempt = 0; attempt < 2; ++attempt) {

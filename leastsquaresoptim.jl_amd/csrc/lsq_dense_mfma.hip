@@ -835,6 +835,31 @@ k_diag_max(const double *__restrict__ C, int n, double *__restrict__ out) {
 
 int lsq_cholesky_blocked_factor(lsq_solver *s, int n, double *d_x, bool allow_tiles);
 
+// split-K slices of k_syrk_mfma<0> on a krows x ncols operand: enough workgroups for ~6 per CU when there are many tiles (their
+// barriers and LDS phases interleave: 42 TFLOP/s at 16384 x 2048), ~2 per CU when the slice reduction would otherwise
+// dominate (4096 x 512)
+int lsq_syrk_slices(const lsq_ctx *c, int krows, int ncols) {
+    const int nt = (ncols + MT - 1) / MT, ntiles = nt * (nt + 1) / 2;
+    const int occ = ntiles >= 128 ? 6 : 2;
+    const int kslices = std::max(1, std::min(512, (occ * c->num_cus + ntiles - 1) / ntiles));
+    return std::min(kslices, std::max(1, krows / (4 * KC)));
+}
+size_t lsq_syrk_partial_elems(int ncols, int kslices) {
+    const int nt = (ncols + MT - 1) / MT, ntiles = nt * (nt + 1) / 2;
+    return (size_t)kslices * ntiles * MT * MT;
+}
+// the partials W[slice][tile] of A'A for ANY column-major operand A (krows x ncols, leading dimension lda), with A'jy -> jx
+// riding in the launch: what lsq_cholesky_blocked does with the dense Jacobian, for a caller that reduces the slices itself
+// (lsq_schur.hip: the border of a bordered handle and the stack of its eliminated rows)
+int lsq_syrk_partials(lsq_ctx *c, const double *A, int lda, int krows, int ncols, int kslices, double *W, const double *jy,
+                      double *jx) {
+    const int nt = (ncols + MT - 1) / MT, ntiles = nt * (nt + 1) / 2;
+    LSQ_LAUNCH((k_syrk_mfma<0>), dim3(ntiles * kslices + ncols), dim3(256), 0, c->stream, A, lda, krows, ncols, 0, kslices, W,
+               (double *)nullptr, 0, jy, jx);
+    LSQ_HIP(hipGetLastError());
+    return LSQ_OK;
+}
+
 // dense_cholesky.jl:43-59: returns LSQ_ENOTPD through *info like the small kernel.  d_x == nullptr: factor only
 // (the caller decides about the solves); d_dmax != nullptr: also max_j (J'J + damp)_jj before the factorisation.
 // d_y: the right-hand side is J'y and d_x does not hold it yet (it is formed here, inside the SYRK launch where that applies)
@@ -843,12 +868,8 @@ int lsq_cholesky_blocked(lsq_solver *s, lsq_mat *J, const double *d_damp, double
     lsq_ctx *c = s->ctx;
     const int m = J->m, n = J->n;
     const int nt = (n + MT - 1) / MT, ntiles = nt * (nt + 1) / 2;
-    // split-K slices: enough workgroups for ~6 per CU when there are many tiles (their barriers and LDS phases interleave:
-    // 42 TFLOP/s at 16384 x 2048), ~2 per CU when the slice reduction would otherwise dominate (4096 x 512)
-    const int occ = ntiles >= 128 ? 6 : 2;
-    int kslices = std::max(1, std::min(512, (occ * c->num_cus + ntiles - 1) / ntiles));
-    kslices = std::min(kslices, std::max(1, m / (4 * KC)));
-    const size_t need = (size_t)kslices * ntiles * MT * MT;
+    const int kslices = lsq_syrk_slices(c, m, n);
+    const size_t need = lsq_syrk_partial_elems(n, kslices);
     if (s->work_elems < need) {
         hipFree(s->d_T);
         LSQ_HIP(hipMalloc(&s->d_T, need * sizeof(double)));

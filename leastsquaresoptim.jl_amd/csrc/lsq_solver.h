@@ -135,9 +135,11 @@ struct lsq_solver {
     // bordered: zeros (the damping and right-hand side of the elimination) followed by the ng x ng block of the shared parameters
     int *d_cov_info = nullptr;
     double *d_cov_buf = nullptr;
-    // --- lsq_sparse_covariance on an LSMR() solver (lsq_cov_sparse.hip), created on first use: the dense Cholesky() solver
-    // (m, n of this one; lsq_dense_solver_alloc) whose d_chol receives J'J and which factors and inverts it
-    lsq_solver *cov_inner = nullptr;
+    // --- a dense Cholesky() solver (lsq_dense_solver_alloc) owned by this one, factoring a Gram matrix that is written into its
+    // d_chol.  lsq_sparse_covariance on an LSMR() solver (lsq_cov_sparse.hip), created on first use: m, n of this one, J'J.
+    // Schur() on a bordered handle (lsq_schur.hip; br_blocks > 0, d_info and d_work as above), created with the solver: n = ng,
+    // the Schur complement of the locals
+    lsq_solver *inner = nullptr;
 };
 int lsq_tri_chol_solve(lsq_solver *s, const double *U, int n, double *d_bx);
 int lsq_tri_chol_fwd_operands(lsq_solver *s, int n, double **z, unsigned long long **slot, unsigned long long *epoch, int **err);
@@ -274,6 +276,9 @@ int lsq_blockdiag_solve_blocks(lsq_ctx *c, lsq_mat *J, bool pivot, const double 
 int lsq_bordered_solver_alloc(lsq_solver *s, const lsq_mat *J);
 int lsq_bordered_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);
 int lsq_bordered_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double *d_cov, double *d_stderr, int *h_info);
+// implemented in lsq_schur.hip
+int lsq_schur_solver_alloc(lsq_solver *s, const lsq_mat *J);
+int lsq_schur_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);
 // implemented in lsq_blockqr.hip
 int lsq_blockqr_solver_alloc(lsq_solver *s, const lsq_mat *J);
 int lsq_blockqr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);

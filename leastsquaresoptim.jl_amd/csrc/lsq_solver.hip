@@ -27,6 +27,7 @@ extern "C" int lsq_solver_create(lsq_ctx *c, lsq_mat *J, int kind, int for_lm, l
     s->m = J->m;
     s->n = J->n;
     int st = (kind == LSQ_LSMR) ? lsq_lsmr_alloc(s) : (kind == LSQ_BLOCK_QR) ? lsq_blockqr_solver_alloc(s, J)
+             : (kind == LSQ_SCHUR) ? lsq_schur_solver_alloc(s, J)
              : blockdiag ? lsq_blockdiag_solver_alloc(s, J) : bordered ? lsq_bordered_solver_alloc(s, J) : lsq_dense_solver_alloc(s);
     if (st != LSQ_OK) {
         delete s;
@@ -42,9 +43,9 @@ extern "C" int lsq_solver_destroy(lsq_solver *s) {
     if (s->kind == LSQ_LSMR) lsq_lsmr_free(s);
     else lsq_dense_solver_free(s);     // (also the block-diagonal solvers: all they own is d_info, freed there)
     hipFree(s->d_cov_info); hipFree(s->d_cov_buf);     // lsq_solver_covariance
-    if (s->cov_inner) {                                // lsq_sparse_covariance
-        lsq_dense_solver_free(s->cov_inner);
-        delete s->cov_inner;
+    if (s->inner) {                                // lsq_sparse_covariance, Schur()
+        lsq_dense_solver_free(s->inner);
+        delete s->inner;
     }
     delete s;
     return LSQ_OK;
@@ -80,6 +81,7 @@ extern "C" int lsq_ldiv(lsq_solver *s, lsq_mat *J, const double *y, double *x, i
         if (s->br_blocks) return lsq_bordered_solve(s, J, y, nullptr, x, nmul);     // (refused: LM only)
         return s->bd_blocks ? lsq_blockdiag_solve(s, J, y, nullptr, x, nmul) : lsq_cholesky_solve(s, J, y, nullptr, x, nmul);
     case LSQ_BLOCK_QR: return lsq_blockqr_solve(s, J, y, nullptr, x, nmul);
+    case LSQ_SCHUR: return lsq_schur_solve(s, J, y, nullptr, x, nmul);             // (refused: LM only)
     default: return lsq_qr_solve(s, J, y, nullptr, x, nmul);
     }
 }
@@ -93,6 +95,7 @@ extern "C" int lsq_ldiv_damped(lsq_solver *s, lsq_mat *J, const double *y, doubl
         if (s->br_blocks) return lsq_bordered_solve(s, J, y, damp, x, nmul);
         return s->bd_blocks ? lsq_blockdiag_solve(s, J, y, damp, x, nmul) : lsq_cholesky_solve(s, J, y, damp, x, nmul);
     case LSQ_BLOCK_QR: return lsq_blockqr_solve(s, J, y, damp, x, nmul);
+    case LSQ_SCHUR: return lsq_schur_solve(s, J, y, damp, x, nmul);
     default: return lsq_qr_solve(s, J, y, damp, x, nmul);
     }
 }
@@ -126,16 +129,16 @@ extern "C" int lsq_solver_stats(const lsq_solver *s, int h_giveups[4], int h_pau
         if (h_giveups) h_giveups[i] = fb[i]->giveups;
         if (h_paused) h_paused[i] = fb[i]->cooldown;
     }
-    if (s->cov_inner) {      // an LSMR() solver after lsq_sparse_covariance: the factorisation of its inner dense solver
-        if (h_giveups) h_giveups[0] += s->cov_inner->fb_tiles.giveups;
-        if (h_paused) h_paused[0] += s->cov_inner->fb_tiles.cooldown;
+    if (s->inner) {      // an LSMR() solver after lsq_sparse_covariance, a Schur() solver: the factorisation of its inner dense solver
+        if (h_giveups) h_giveups[0] += s->inner->fb_tiles.giveups;
+        if (h_paused) h_paused[0] += s->inner->fb_tiles.cooldown;
     }
     return LSQ_OK;
 }
 
 extern "C" int lsq_solver_chol_path(const lsq_solver *s, int *path) {
     if (!s || !path) { lsq_set_error("lsq_solver_chol_path: null argument"); return LSQ_EARG; }
-    *path = s->cov_inner ? s->cov_inner->last_chol_path : s->last_chol_path;   // (LSMR() after lsq_sparse_covariance: its factorisation)
+    *path = s->inner ? s->inner->last_chol_path : s->last_chol_path;   // (LSMR() after lsq_sparse_covariance, Schur(): the inner solver's factorisation)
     return LSQ_OK;
 }
 
