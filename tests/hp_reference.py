@@ -13,6 +13,15 @@ Every result is longdouble.
                                    and the shared block of inv(J'J)
     lstsq_qr(A, y)                 min ||A x - y|| by Householder QR (no pivoting: full column rank is the caller's promise);
                                    y may be a matrix of right-hand sides: one factorisation, one solution per column
+    minnorm_solve(W, c)            the minimum-norm z with W z = c, W of full ROW rank: Householder QR of W'
+    minnorm_from_factors(B, W, y)  A^+ y = W^+ B^+ y for A = B W given by two full-rank factors (rank-deficient A, exact rank:
+                                   tests/rankdef_common.py); minnorm_gram_solve: the same W^+ by the Cholesky factor of W W'
+    pivoted_truncated_solve(A, y, jpvt, r)
+                                   the xGELSY solution in longdouble for GIVEN pivots and rank: r Householder steps on A[:, jpvt],
+                                   then the minimum-norm solution of [R11 R12] z = (Q'y)(1:r)
+    normal_solve_refined(A, y, G), minnorm_gram_refined(W, c, G)
+                                   the two solves above from a Gram matrix that the caller formed EXACTLY, plus one step of
+                                   refinement: the affordable form for operands with hundreds of columns
 """
 import numpy as np
 
@@ -151,3 +160,85 @@ def lstsq_qr(A, y):
         RT[j:, j:] -= 2 * np.outer(RT[j:, j:] @ v, v)
     R = RT.T
     return solve_upper(np.triu(R[:n, :n]), R[:n, n] if np.ndim(y) == 1 else R[:n, n:])
+
+
+def _reflect(RT, steps):
+    """The first `steps` Householder reflectors of the QR of RT' (RT holds the columns as its rows, as in lstsq_qr), applied in
+    place; returns their unit vectors v_j (H_j = I - 2 v_j v_j' on the entries j..)."""
+    vs = []
+    for j in range(steps):
+        v = RT[j, j:].copy()
+        alpha = np.sqrt(v @ v)
+        if alpha == 0:
+            raise np.linalg.LinAlgError("longdouble QR: column %d is zero" % j)
+        v[0] += alpha if v[0] >= 0 else -alpha
+        v = v / np.sqrt(v @ v)
+        RT[j:, j:] -= 2 * np.outer(RT[j:, j:] @ v, v)
+        vs.append(v)
+    return vs
+
+
+def minnorm_solve(W, c):
+    """The minimum-norm z with W z = c for W (r x n, full row rank: the caller's promise): W' = Q [R; 0] by Householder, then
+    z = Q [R'^-1 c; 0].  Backward stable: cond(W) enters once (the Cholesky factor of W W' would square it)."""
+    RT = np.ascontiguousarray(ld(W))            # the rows of W are the columns of W'
+    r, n = RT.shape
+    vs = _reflect(RT, r)
+    R = np.triu(RT[:, :r].T)
+    z = np.zeros(n, dtype=LD)
+    z[:r] = solve_upper_t(R, ld(c))
+    for j in range(r - 1, -1, -1):
+        z[j:] -= 2 * vs[j] * (vs[j] @ z[j:])
+    return z
+
+
+def minnorm_gram_solve(W, c):
+    """The same z = W'(W W')^-1 c by the longdouble Cholesky factor of W W' (cond(W)^2: for well-conditioned W only)."""
+    W = ld(W)
+    return W.T @ chol_solve(cholesky_upper(W @ W.T), ld(c))
+
+
+def minnorm_from_factors(B, W, y, z=None):
+    """A^+ y for A = B W, B (m x r) of full column rank and W (r x n) of full row rank: A^+ = W^+ B^+, so z = B^+ y by lstsq_qr
+    (pass it in to reuse it for another W) and x = W^+ z by minnorm_solve.  No rank decision, no pivoting: the reference does
+    not depend on the algorithm under test."""
+    if z is None:
+        z = lstsq_qr(B, y)
+    return minnorm_solve(W, z)
+
+
+def pivoted_truncated_solve(A, y, jpvt, r):
+    """xGELSY's answer for pivots jpvt and rank r, in longdouble: r Householder steps on [A[:, jpvt] | y], the minimum-norm
+    solution of [R11 R12] z = (Q'y)(1:r), x[jpvt] = z."""
+    A = ld(A)
+    n = A.shape[1]
+    jpvt = np.asarray(jpvt)
+    x = np.zeros(n, dtype=LD)
+    if r == 0:
+        return x
+    RT = np.ascontiguousarray(np.column_stack([A[:, jpvt], ld(y)]).T)
+    _reflect(RT, r)
+    x[jpvt] = minnorm_solve(np.triu(RT[:n, :r].T), RT[n, :r])
+    return x
+
+
+def normal_solve_refined(A, y, G, damp=None):
+    """(A'A + diag(damp)) x = A'y with the Gram matrix G = A'A GIVEN -- exact where the caller can form it exactly (integer
+    factors) -- by its Cholesky factor and one step of refinement on the residual A'(y - A x) - damp x, formed in longdouble
+    without G.  For the large operands of tests/rankdef_common.py, where n Householder steps in longdouble take a quarter of a
+    minute: the Cholesky factor costs n^3 / 3, and the refinement step takes the error from cond(G) 2^-64 to its square."""
+    A, y, G = ld(A), ld(y), ld(G)
+    d = np.zeros(A.shape[1], dtype=LD) if damp is None else ld(damp)
+    U = cholesky_upper(G + np.diag(d))
+    x = chol_solve(U, A.T @ y)
+    return x + chol_solve(U, A.T @ (y - A @ x) - d * x)
+
+
+def minnorm_gram_refined(W, c, G):
+    """The minimum-norm z = W'u, (W W') u = c with G = W W' GIVEN (exact for an integer W), one step of refinement on
+    c - W (W'u)."""
+    W, c = ld(W), ld(c)
+    U = cholesky_upper(G)
+    u = chol_solve(U, c)
+    u = u + chol_solve(U, c - W @ (W.T @ u))
+    return W.T @ u
