@@ -131,8 +131,26 @@ int lsq_mat_set_values_async(lsq_mat *J, const double *h_pinned_values);
 int lsq_mat_upload_wait(lsq_mat *J);
 /* Device pointer to the values a device-side g! writes (dense buffer / CSC nzval) ... */
 double *lsq_mat_values(lsq_mat *J);
-/* ... after which the CSR mirror must be refreshed (no-op for dense). */
+/* ... after which the CSR mirror must be refreshed (no-op for dense).
+ * FRESHNESS CONTRACT.  A handle keeps its values in several layouts (CSC order, row and column mirrors or sliced layouts, the
+ * stored V of a multiplied-out column scale, the dense buffer), and which of them is the authority changes with the last
+ * mutation.  What a caller may rely on: after ANY entry of this header that changes the values -- lsq_mat_set_values / _async,
+ * lsq_mat_values + writes + lsq_mat_refresh, lsq_mat_set_colscale / lsq_mat_colscale_changed, lsq_fd_jacobian, the g! of
+ * lsq_model_g -- every reader (lsq_mat_get_values, lsq_mul, lsq_colsumabs2, lsq_rowsumabs2, lsq_ldiv*, lsq_sparse_gram, the
+ * covariance entries, the loops) sees those values and nothing older, in whatever order mutations and readers are mixed, and
+ * gives the bits it gives on a freshly created handle holding the same V and s.
+ * lsq_mat_values returns the values as they are at that moment; the pointer is for writing until the next entry that changes
+ * the values through another route (a g! of lsq_model_g in particular may write the mirrors only): take it again after that.
+ * lsq_mat_refresh first brings the CSC-ordered copy up to date with such a g!, then takes it as the authority: called with
+ * nothing written it changes no value (so does lsq_mat_set_colscale(J, NULL) on a handle that has no scale). */
 int lsq_mat_refresh(lsq_mat *J);
+/* Which layouts the handle has built and which mode it is in (host code: launches nothing, waits for nothing, changes nothing):
+ * h_out[0] kind (0 dense, 1 CSC -- block-diagonal and bordered handles included --, 2 operator); [1] sliced rows built (J*x),
+ * [2] their column windows, [3] output rows per block; [4] sliced columns built (J'y), [5] their gather windows, [6] column
+ * blocks per gather window; [7] windows of the window-blocked CSC (0: not built); [8] / [9] launch plan of the row / column
+ * segments (0 stream, 1 wave, 2 block; -1 for a handle that is not CSC); [10] column scale: 0 none, 1 fused (read inside the
+ * kernels), 2 multiplied out; [11] 1 when the CSC-ordered copy is current, 0 after a g! that wrote the mirrors only. */
+int lsq_mat_layout(const lsq_mat *J, int h_out[12]);
 
 /* ---- column-scaled Jacobians J = V diag(s) ----
  * Models of the form r(x) = V phi(x) - b (phi elementwise) have J(x) = V diag(phi'(x)): the pattern AND the stored values V

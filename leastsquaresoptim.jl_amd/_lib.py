@@ -127,6 +127,7 @@ def lib():
         "lsq_emul": (i, [vp, i, vp, vp, vp]),
         "lsq_mat_values": (vp, [vp]),
         "lsq_mat_refresh": (i, [vp]),
+        "lsq_mat_layout": (i, [vp, c_ip]),
         "lsq_mat_set_colscale": (i, [vp, vp]),
         "lsq_mat_colscale_changed": (i, [vp]),
         "lsq_mul": (i, [vp, i, d, vp, d, vp]),

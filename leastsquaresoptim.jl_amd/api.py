@@ -501,6 +501,18 @@ class PinnedBuffer:
             pass
 
 
+def mat_layout(h):
+    """lsq_mat_layout of a raw handle as a dict (DeviceMatrix.layout(); a TanhProblem's `.J` takes it too)."""
+    o = (C.c_int * 12)()
+    check(lib().lsq_mat_layout(h, o))
+    plan = {-1: None, 0: "stream", 1: "wave", 2: "block"}
+    return dict(kind={0: "dense", 1: "csc", 2: "operator"}[o[0]],
+                srows=dict(active=bool(o[1]), ncw=o[2], wrows=o[3]),
+                scols=dict(active=bool(o[4]), ngw=o[5], ncb=o[6]),
+                nwin=o[7], csr_plan=plan[o[8]], csc_plan=plan[o[9]],
+                colscale={0: None, 1: "fused", 2: "materialising"}[o[10]], csc_fresh=bool(o[11]))
+
+
 class DeviceMatrix:
     """Jacobian handle: dense column-major or CSC (+ CSR mirror) -- `HipDense` / `HipCSC`."""
 
@@ -569,6 +581,14 @@ class DeviceMatrix:
         out = np.empty(self.nnz)
         check(lib().lsq_mat_get_values(self.h, out.ctypes.data_as(_lib.c_dp)))
         return out
+
+    def refresh(self):
+        """lsq_mat_refresh: after a device-side write through lsq_mat_values."""
+        check(lib().lsq_mat_refresh(self.h))
+
+    def layout(self):
+        """lsq_mat_layout: which layouts the handle built and which mode it is in (host code, changes nothing)."""
+        return mat_layout(self.h)
 
     def blockdiag_info(self):
         """lsq_mat_blockdiag_info: (nblocks, mb, nb); (0, 0, 0) for a handle that is not block-diagonal."""

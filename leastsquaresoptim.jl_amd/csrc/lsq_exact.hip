@@ -33,7 +33,9 @@ static bool exact_enabled() { return g_exact_override >= 0 ? g_exact_override !=
 
 bool lsq_small_vec(long long n) { return exact_enabled() && n <= LSQ_EXACT_MAX_DIM; }
 bool lsq_small_mat(const lsq_mat *J) {
-    return J->kind != LSQ_MAT_OP && exact_enabled() && J->m <= LSQ_EXACT_MAX_DIM && J->n <= LSQ_EXACT_MAX_DIM && J->nnz <= LSQ_EXACT_MAX_NNZ;
+    // (sliced rows, which only LSQ_SELL_FORCE builds on a pattern this small, have freed the CSR mirror the reference-order
+    //  kernels read: such a handle keeps the sliced kernels in either mode)
+    return J->kind != LSQ_MAT_OP && !J->srows.active && exact_enabled() && J->m <= LSQ_EXACT_MAX_DIM && J->n <= LSQ_EXACT_MAX_DIM && J->nnz <= LSQ_EXACT_MAX_NNZ;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -738,8 +738,11 @@ extern "C" int lsq_mat_set_colscale(lsq_mat *J, const double *d_s) {
     return lsq_mat_colscale_changed(J);
 }
 
-extern "C" int lsq_mat_refresh(lsq_mat *J) {
-    LSQ_RANGE("lsq_mat_refresh");
+// The values were (re)written in CSC order / dense column-major (V of a materialising scale in d_cs_base): multiply out if
+// needed and rebuild every mirror.  The CSC-ordered copy becomes the authority, so whoever calls this has either overwritten
+// ALL of it (uploads: they set csc_fresh themselves, nothing of a lazy g! may be copied over the new values) or has made it
+// current first (lsq_mat_refresh, lsq_fd_jacobian: lsq_ensure_csc).
+static int mat_values_written(lsq_mat *J) {
     J->version++;
     J->base_version++;
     if (J->d_cs_base) LSQ_TRY(colscale_multiply_out(J));   // (the caller wrote V: multiply out again)
@@ -748,6 +751,36 @@ extern "C" int lsq_mat_refresh(lsq_mat *J) {
         J->csc_fresh = true;  // the CSC copy is the authority here
     }
     return lsq_ensure_csr(J);
+}
+
+extern "C" int lsq_mat_refresh(lsq_mat *J) {
+    LSQ_RANGE("lsq_mat_refresh");
+    // a device g! may have written the mirrors only since the pointer of lsq_mat_values was taken (or the caller never took
+    // one: lsq_mat_set_colscale(J, NULL) on a handle without a scale): bring the CSC-ordered copy up to date BEFORE it is
+    // declared the authority, or the mirrors would be rebuilt from the values of before that g!
+    LSQ_TRY(lsq_ensure_csc(J));
+    return mat_values_written(J);
+}
+
+extern "C" int lsq_mat_layout(const lsq_mat *J, int h_out[12]) {
+    if (!J || !h_out) {
+        lsq_set_error("lsq_mat_layout: null argument");
+        return LSQ_EARG;
+    }
+    const bool csc = J->kind == LSQ_MAT_CSC;
+    h_out[0] = J->kind;
+    h_out[1] = csc && J->srows.active;
+    h_out[2] = h_out[1] ? J->srows.ncw : 0;
+    h_out[3] = h_out[1] ? J->srows.wrows : 0;
+    h_out[4] = csc && J->scols.active;
+    h_out[5] = h_out[4] ? J->scols.ngw : 0;
+    h_out[6] = h_out[4] ? J->scols.ncb : 0;
+    h_out[7] = csc ? J->nwin : 0;
+    h_out[8] = csc ? J->csr.plan : -1;
+    h_out[9] = csc ? J->csc.plan : -1;
+    h_out[10] = !J->d_cs_user ? 0 : (J->d_colscale ? 1 : 2);
+    h_out[11] = csc ? (int)J->csc_fresh : 1;
+    return LSQ_OK;
 }
 
 extern "C" int lsq_mat_set_values(lsq_mat *J, const double *h) {
@@ -760,7 +793,7 @@ extern "C" int lsq_mat_set_values(lsq_mat *J, const double *h) {
     if (J->nnz)
         LSQ_HIP(hipMemcpyAsync(dst, h, J->nnz * sizeof(double), hipMemcpyHostToDevice, J->ctx->stream));
     LSQ_HIP(hipStreamSynchronize(J->ctx->stream));  // h is borrowed for the call only
-    return lsq_mat_refresh(J);
+    return mat_values_written(J);                   // (every stored value replaced: nothing older is worth rebuilding)
 }
 
 extern "C" int lsq_mat_set_values_async(lsq_mat *J, const double *h) {
@@ -786,7 +819,7 @@ extern "C" int lsq_mat_set_values_async(lsq_mat *J, const double *h) {
     LSQ_HIP(hipEventRecord(c->copy_done, c->copy_stream));
     LSQ_HIP(hipStreamWaitEvent(c->stream, c->copy_done, 0));
     J->upload_pending = true;
-    return lsq_mat_refresh(J);     // (device work only: the mirrors are rebuilt behind the copy)
+    return mat_values_written(J);  // (device work only: the mirrors are rebuilt behind the copy)
 }
 
 extern "C" int lsq_mat_upload_wait(lsq_mat *J) {

@@ -433,6 +433,9 @@ def test_column_scaled_jacobian(ctx, kind, monkeypatch):
             monkeypatch.setenv("LSQ_NO_SELL", "1")
         if kind == "wide":     # x passes through LDS in four column windows (what n > 12160 gets)
             monkeypatch.setenv("LSQ_SELL_XMAX", "400")
+            # (1.2e6 entries over four windows are fewer than lsq_csc_create wants before it builds column windows by itself:
+            #  without this switch the sliced rows were not built and the case ran the segment kernels -- layout() below)
+            monkeypatch.setenv("LSQ_SELL_WIDE", "1")
     elif kind == "small":
         m, n = 300, 20
         S = rand_csc(m, n, 0.3, 6)
@@ -442,6 +445,14 @@ def test_column_scaled_jacobian(ctx, kind, monkeypatch):
     J = lsq.DeviceMatrix(ctx, S)
     monkeypatch.delenv("LSQ_NO_SELL", raising=False)
     monkeypatch.delenv("LSQ_SELL_XMAX", raising=False)
+    monkeypatch.delenv("LSQ_SELL_WIDE", raising=False)
+    lay = J.layout()
+    assert lay["kind"] == ("dense" if kind == "dense" else "csc") and lay["colscale"] is None
+    assert (lay["srows"]["active"], lay["scols"]["active"]) == ((True, True) if kind in ("sliced", "wide") else (False, False)), lay
+    if kind in ("sliced", "wide"):
+        assert lay["srows"]["ncw"] == (4 if kind == "wide" else 1), lay
+    if kind == "segments":
+        assert lay["nwin"] > 1, lay              # (m > 131072 without sliced columns: the window-blocked CSC takes J'y)
     V = S.tocsc() if kind != "dense" else S
     x, y = rng.standard_normal(n), rng.standard_normal(m)
     damp = rng.uniform(0.5, 2.0, n)
@@ -467,6 +478,7 @@ def test_column_scaled_jacobian(ctx, kind, monkeypatch):
     s1 = rng.uniform(0.2, 1.5, n)
     ds = lsq.DeviceVector(ctx, n, s1)
     J.set_colscale(ds)
+    assert J.layout()["colscale"] == ("fused" if kind in ("sliced", "wide") else "materialising"), J.layout()
     vals0 = J.values()
     assert np.array_equal(vals0, V.data if kind != "dense" else np.asfortranarray(V).reshape(-1, order="F"))   # still V
     check_all(V, s1)
@@ -483,6 +495,7 @@ def test_column_scaled_jacobian(ctx, kind, monkeypatch):
         J.set_values(np.asfortranarray(V2).reshape(-1, order="F"))
     check_all(V2, s2)
     J.set_colscale(None)
+    assert J.layout()["colscale"] is None
     check_all(V2, np.ones(n))
     J.free()
 

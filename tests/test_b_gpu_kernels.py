@@ -14,6 +14,24 @@ from gpu_common import GRID, OPT, SOL, compare, gpu_run, lsq, oracle_run, rand_c
 pytestmark = pytest.mark.gpu
 
 
+def assert_sliced_layout(J, S, rows=None, grows=None, xmax=None, label=None):
+    """DeviceMatrix.layout(): LSQ_SELL_FORCE built what the test is about.  The sliced columns always (a pattern with entries);
+    the sliced rows where the rows keep the stream plan (fewer than 48 entries per row on average, or LSQ_PLAN_CSR=stream) and
+    x needs at most 32 column windows; block and window sizes as the switches ask."""
+    lay, (m, n) = J.layout(), S.shape
+    assert lay["kind"] == "csc" and lay["scols"]["active"] == (S.nnz > 0), (label, lay)
+    ncw = -(-n // min(12160, max(64, xmax))) if xmax else 1
+    want_rows = S.nnz > 0 and (lay["csr_plan"] == "stream") and ncw <= 32
+    assert lay["srows"]["active"] == want_rows, (label, lay)
+    if want_rows:
+        assert lay["srows"]["ncw"] == ncw, (label, lay)
+        if rows:
+            assert lay["srows"]["wrows"] == min(4096, max(64, rows & ~63)), (label, lay)
+    if grows and S.nnz > 0:
+        assert lay["scols"]["ngw"] == -(-m // min(16384, max(64, grows & ~7))), (label, lay)
+    return lay
+
+
 # ------------------------------------------------------------------------------- kernels
 @pytest.mark.parametrize("window_rows", [None, 1024, 96])
 @pytest.mark.parametrize("plan", ["stream", "wave", "block", None])
@@ -82,6 +100,8 @@ def test_sliced_layouts(ctx, m, n, density, rows, grows):
     finally:
         for k in ("LSQ_SELL_FORCE", "LSQ_SELL_ROWS", "LSQ_SELL_GROWS"):
             os.environ.pop(k, None)
+    lay = assert_sliced_layout(J, S, rows, grows)
+    assert lay["srows"]["active"] == (S.nnz / m < 48)      # (64 x 3000 keeps the wave-per-row plan: sliced columns only)
     lsq.set_exact(False)
     try:
         A = O.Mat.from_scipy(S)
@@ -134,13 +154,18 @@ def test_sliced_rows_column_windows(ctx, m, n, density, xmax, rows):
     S.sort_indices()
     S.eliminate_zeros()
     os.environ["LSQ_SELL_FORCE"], os.environ["LSQ_SELL_XMAX"] = "1", str(xmax)
+    # (64 x 3000 and 5000 x 400 average 60 and 120 entries per row: without the stream plan of the rows the sliced rows, and
+    #  with them the column windows this test is about, were not built there -- DeviceMatrix.layout() showed it)
+    os.environ["LSQ_PLAN_CSR"] = "stream"
     if rows:
         os.environ["LSQ_SELL_ROWS"] = str(rows)
     try:
         J = lsq.DeviceMatrix(ctx, S)
     finally:
-        for k in ("LSQ_SELL_FORCE", "LSQ_SELL_ROWS", "LSQ_SELL_XMAX"):
+        for k in ("LSQ_SELL_FORCE", "LSQ_SELL_ROWS", "LSQ_SELL_XMAX", "LSQ_PLAN_CSR"):
             os.environ.pop(k, None)
+    lay = assert_sliced_layout(J, S, rows, None, xmax)
+    assert lay["srows"]["active"] and lay["srows"]["ncw"] > 1, lay
     lsq.set_exact(False)
     try:
         A = O.Mat.from_scipy(S)
@@ -210,11 +235,13 @@ def test_sliced_layouts_random_patterns(ctx):
             os.environ["LSQ_SELL_GROWS"] = str(int(rng.choice([64, 512, 8192])))
             if case % 2:      # every other case: x in column windows narrower than n (k_sell_rows_wide)
                 os.environ["LSQ_SELL_XMAX"] = str(int(rng.integers(64, 300)))
+            asked = {k: int(os.environ[k]) for k in ("LSQ_SELL_ROWS", "LSQ_SELL_GROWS", "LSQ_SELL_XMAX") if k in os.environ}
             try:
                 J = lsq.DeviceMatrix(ctx, S)
             finally:
                 for k in ("LSQ_SELL_FORCE", "LSQ_SELL_ROWS", "LSQ_SELL_GROWS", "LSQ_SELL_XMAX"):
                     os.environ.pop(k, None)
+            assert_sliced_layout(J, S, asked["LSQ_SELL_ROWS"], asked["LSQ_SELL_GROWS"], asked.get("LSQ_SELL_XMAX"), (case, m, n))
             x, y = rng.standard_normal(n), rng.standard_normal(m)
             dx, dy = lsq.DeviceVector(ctx, n, x), lsq.DeviceVector(ctx, m, y)
             out = lsq.mul_(lsq.DeviceVector(ctx, m, y), J, dx, 0.75, 1.25).get()

@@ -50,6 +50,30 @@ LAYOUTS.update({"window 96": {"LSQ_WINDOW_ROWS": "96"},
                 "sliced xmax 64": {"LSQ_SELL_FORCE": "1", "LSQ_SELL_XMAX": "64"}})
 
 
+def assert_layout(lay, layout, m, n, nnz, scaled):
+    """DeviceMatrix.layout() says what the switches of LAYOUTS[layout] were to build (lsq_csc_create): the plans as named; the
+    CSC windows of LSQ_WINDOW_ROWS where m exceeds a window; the sliced columns under LSQ_SELL_FORCE, and the sliced rows where
+    the rows keep the stream plan (fewer than 48 entries per row on average: not 64 x 3000) and x needs at most 32 column
+    windows; the fused column scale exactly where both sliced layouts exist."""
+    env = LAYOUTS[layout]
+    assert lay["kind"] == "csc"
+    for key, plan in (("csr_plan", env.get("LSQ_PLAN_CSR")), ("csc_plan", env.get("LSQ_PLAN_CSC"))):
+        assert plan is None or lay[key] == plan, (layout, lay)
+    rw = int(env.get("LSQ_WINDOW_ROWS", 0))
+    assert lay["nwin"] == (-(-m // rw) if rw and m > rw else 0), (layout, lay)
+    forced = "LSQ_SELL_FORCE" in env
+    ncw = -(-n // int(env["LSQ_SELL_XMAX"])) if "LSQ_SELL_XMAX" in env else 1
+    rows = forced and nnz / m < 48 and ncw <= 32
+    assert lay["scols"]["active"] == forced and lay["srows"]["active"] == rows, (layout, lay)
+    if rows:
+        assert lay["srows"]["ncw"] == ncw, (layout, lay)
+        if "LSQ_SELL_ROWS" in env:
+            assert lay["srows"]["wrows"] == int(env["LSQ_SELL_ROWS"]), (layout, lay)
+    if forced and "LSQ_SELL_GROWS" in env:
+        assert lay["scols"]["ngw"] == -(-m // int(env["LSQ_SELL_GROWS"])), (layout, lay)
+    assert lay["colscale"] == ((("fused" if rows else "materialising")) if scaled else None), (layout, lay)
+
+
 class ProductRef:
     """The operand as the plain handle stores it (fl(r_i s_ik c_k)) and as the column-scaled handle means it (fl(r_i s_ik) c_k,
     unrounded), x, y, and per (scaled handle, trans) the longdouble reference, the magnitude and the entry counts."""
@@ -107,6 +131,7 @@ def test_sparse_products_per_element(ctx, monkeypatch, m, n, density, layout, sc
         if scaled:
             ds = lsq.DeviceVector(ctx, n, c)
             J.set_colscale(ds)
+        assert_layout(J.layout(), layout, m, n, P.nnz, scaled)
         judge_both_products(ctx, J, ref, scaled, "%dx%d %s%s" % (m, n, layout, " colscale" if scaled else ""))
         J.free()
     finally:

@@ -3,7 +3,7 @@ library.  The cases and their certified (iter, istop), margins and e_ref come fr
 device by tests/test_lsmr_stops_host.py; x_hp is the longdouble twin (tests/lsmr_reference.py) at the same iteration count.
 
 Drivers -- which copy of the seven rules decides, and how the test KNOWS it ran (info()["lsmr_path"], lsq_solver_lsmr_path:
-no other accessor says which iteration ran, and the sliced layouts of a handle cannot be queried from Python at all):
+no other accessor says which iteration ran; the layouts a handle built are DeviceMatrix.layout(), lsq_mat_layout):
     csc               unsliced CSC handle                                   lsmr_commit (k_lsmr_update)      "four-launch"
     sliced_four       LSQ_SELL_FORCE=1 handle, LSQ_LSMR_FOUR_LAUNCHES=1     lsmr_commit                      "four-launch"
                       (that the handle IS sliced: the same handle without the switch answers "three-launch", which

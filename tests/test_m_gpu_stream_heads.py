@@ -97,7 +97,12 @@ def both(ctx, J, n, seed):
 
 
 def both_layouts_built(ctx, J, n):
-    """An LSMR solve on J took the three-launch driver: sliced rows (one column window) and sliced columns are both active."""
+    """DeviceMatrix.layout() shows what ENV asked for -- sliced rows in blocks of 128 with one column window, sliced columns
+    with three gather windows of 256 rows -- and an LSMR solve on J took the three-launch driver, which needs both."""
+    lay = J.layout()
+    if not (lay["srows"]["active"] and lay["scols"]["active"] and
+            (lay["srows"]["ncw"], lay["srows"]["wrows"], lay["scols"]["ngw"]) == (1, 128, 3)):
+        return False
     sv = lsq.AllocatedSolver(J, lsq.LSMR(), for_lm=False)
     try:
         y = np.random.default_rng(3).standard_normal(M)
