@@ -40,6 +40,9 @@ typedef struct lsq_model lsq_model;   /* built-in device-side f!/g! (synthetic b
 /* types.jl:79-86; LSQ_BLOCK_QR: QR() per block of a block-diagonal handle (lsq_blockdiag_create), one rank decision per block;
  * LSQ_SCHUR: Cholesky()'s damped solve on a bordered handle (lsq_blockdiag_bordered_create) with any number of shared columns */
 typedef enum { LSQ_QR = 0, LSQ_CHOLESKY = 1, LSQ_LSMR = 2, LSQ_BLOCK_QR = 3, LSQ_SCHUR = 4 } lsq_solver_kind;
+/* one more solver kind (lsq_solver_create and lsq_optimize take the kind as an int): the backward-stable direct solver on a
+ * bordered handle, Householder QR of the locals block by block and a dense QR() of what is left of the border */
+enum { LSQ_BORDERED_QR = 5 };
 typedef enum { LSQ_DOGLEG = 0, LSQ_LEVENBERG_MARQUARDT = 1 } lsq_optimizer_kind;   /* types.jl:90-98 */
 
 const char *lsq_last_error(void);
@@ -113,7 +116,25 @@ int lsq_mat_blockdiag_info(const lsq_mat *J, int *nblocks, int *mb, int *nb);
  * lsq_solver_stats index 0 counts a give-up of its one-launch form (S is then formed again and factored by panel launches).
  * LSQ_EARG: any other handle (dense, plain CSC, block-diagonal, operator), nb > 64, for_lm = 0 / lsq_ldiv / Dogleg (the text
  * of LSQ_CHOLESKY's refusal, for the same reason), lsq_optimize_batched, lsq_solver_covariance (lsq_sparse_covariance on an
- * LSMR() solver serves the handle), a handle of another shape than the solver was created for. */
+ * LSMR() solver serves the handle), a handle of another shape than the solver was created for.
+ * LSQ_BORDERED_QR is the backward-stable direct solver on this handle (for_lm = 1, nb <= 64, ANY ng >= 1 and mb >= 1; memory:
+ * a copy of the values for the reflectors and the transformed border, B*nb*ng doubles for the triangle's border rows, and
+ * the inner QR()'s (m + ng)*ng): lsq_ldiv_damped returns the minimiser of || [J S; diag(sqrt(damp))] x - [y; 0] ||_2 (S: the
+ * handle's column scale, if set) by Householder reflectors -- neither J'J nor any part of it is formed, so the solve pays
+ * cond(J) where LSQ_CHOLESKY and LSQ_SCHUR pay cond(J)^2.  Per block the rows of [J_b C_b y_b] are eliminated against a
+ * triangle that starts as diag(sqrt(damp_b)), the locals unpivoted (Householder QR is columnwise backward stable without
+ * pivoting); the transformed border rows, a dense (B*mb) x ng matrix, go with the last ng damping values to ONE damped solve
+ * of a dense LSQ_QR solver this one owns; then x_b = inv(R_b) (z_b - W_b x_g).  nmul = 1, damp is not written, stream
+ * order, no floating-point atomics.  A diagonal entry of some R_b that is exactly zero or not finite -- possible only where
+ * a damping value is zero or an operand is not finite -- is LSQ_ERANK, the message names the 1-based stacked column
+ * b*nb + k, the lowest one wins, and the solver stays usable; the shared part follows LSQ_QR's rules (a rank decision, the
+ * minimum-norm solution) and never fails on rank.  lsq_ldiv_damped and lsq_optimize with LSQ_LEVENBERG_MARQUARDT take it
+ * (bounds and g = NULL included; LM's damping is at least MIN_DIAGONAL * mean(dtd) > 0, so a fit on finite values cannot
+ * reach LSQ_ERANK).  lsq_solver_info reports qr_rank = B*nb + the inner rank, lsq_solver_blockdiag_path 6 (after LSQ_ERANK
+ * the block), lsq_solver_qr_path / lsq_solver_qr_panel the inner solver's values, lsq_solver_stats (indices 2 and 3) its
+ * give-ups.  LSQ_EARG: any other handle, nb > 64, for_lm = 0 / lsq_ldiv / Dogleg (LSQ_CHOLESKY's text, for the same reason),
+ * lsq_optimize_batched, lsq_solver_covariance / lsq_dense_covariance / lsq_dense_qr_covariance / lsq_sparse_covariance, a
+ * handle of another shape than the solver was created for. */
 int lsq_blockdiag_bordered_create(lsq_ctx *ctx, int nblocks, int mb, int nb, int ng, lsq_mat **out);
 /* all 0 for any other handle */
 int lsq_mat_bordered_info(const lsq_mat *J, int *nblocks, int *mb, int *nb, int *ng);
@@ -266,7 +287,8 @@ typedef int (*lsq_device_allreduce_callback)(double *d_buf, int count, void *hip
 /* row-sharded operator-level use (lsq_ldiv / lsq_ldiv_damped with LSMR on a row block J_p; y is the local slice, x the
  * replicated solution): installs the all-reduce hook of lsq_options.row_allreduce on this solver.  NULL removes it. */
 int lsq_solver_set_row_allreduce(lsq_solver *s, lsq_device_allreduce_callback cb, void *user, long long global_rows);
-/* diagnostics of the last solve: LSMR istop / iterations, QR numerical rank (LSQ_BLOCK_QR: the sum of the block ranks) */
+/* diagnostics of the last solve: LSMR istop / iterations, QR numerical rank (LSQ_BLOCK_QR: the sum of the block ranks;
+ * LSQ_BORDERED_QR: B*nb + the rank of the inner QR()) */
 int lsq_solver_info(const lsq_solver *s, int *lsmr_iter, int *lsmr_istop, int *qr_rank);
 /* which factorisation the last QR solve used (dense_qr.jl:37,83 always runs geqp3; this build only needs the
  * pivoted sweep when the rank decision is open):  0 none yet, 1 one-stage pivoted Householder,
@@ -289,7 +311,8 @@ int lsq_solver_chol_path(const lsq_solver *s, int *path);
  * general preconditioner (lsq_lsmr_general.hip).  Read-only; the tests use it to know which copy of the stopping rules ran. */
 int lsq_solver_lsmr_path(const lsq_solver *s, int *path);
 /* diagnostics of the last block solve: which path (0 none yet, 1 batched unpivoted LM, 2 batched pivoted Dogleg, 3 batched
- * per-block pivoted QR: LSQ_BLOCK_QR, block = -1, 4 bordered Schur, LM: lsq_blockdiag_bordered_create, 5 the same by LSQ_SCHUR) and, after LSQ_ENOTPD /
+ * per-block pivoted QR: LSQ_BLOCK_QR, block = -1, 4 bordered Schur, LM: lsq_blockdiag_bordered_create, 5 the same by LSQ_SCHUR,
+ * 6 bordered Householder elimination + inner QR(): LSQ_BORDERED_QR) and, after LSQ_ENOTPD /
  * LSQ_ERANK, the block that decided it (path 4: nblocks when the Schur factor of the shared columns failed) (else -1) */
 int lsq_solver_blockdiag_path(const lsq_solver *s, int *path, int *block);
 /* LSQ_BLOCK_QR: the numerical rank of every block in the last solve (h_ranks: nblocks ints; -1 before the first solve).

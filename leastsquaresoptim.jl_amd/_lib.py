@@ -28,7 +28,7 @@ PRECOND_UPDATE_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_
 PRECOND_LDIV_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)                # (d_out, d_in, user)
 
 OK, EDIM, ENOTPD, ERANK, ENONFINITE, EBOUNDS, EHIP, EARG, ECALLBACK, ERCCL = range(10)
-QR, CHOLESKY, LSMR, BLOCK_QR, SCHUR = 0, 1, 2, 3, 4
+QR, CHOLESKY, LSMR, BLOCK_QR, SCHUR, BORDERED_QR = 0, 1, 2, 3, 4, 5
 DOGLEG, LEVENBERG_MARQUARDT = 0, 1
 
 

@@ -53,6 +53,16 @@ class Schur(AbstractSolver):
     kind = _lib.SCHUR
 
 
+class BorderedQR(AbstractSolver):
+    """The backward-stable direct solver on a BorderedBlockDiagonal Jacobian (nb <= 64, any ng; LevenbergMarquardt only): the
+    damped solve as the least-squares problem min ||[J; diag(sqrt(damp))] x - [y; 0]|| by Householder reflectors.  The locals
+    are eliminated block by block (unpivoted) against a triangle that starts as diag(sqrt(damp_b)), the transformed border goes
+    to one dense QR() solve, then the locals are substituted back.  J'J is never formed: the error grows with cond(J) where
+    Cholesky() and Schur() pay cond(J)^2.  A local column that is zero with zero damping, or a non-finite value, raises
+    RankDeficientException with the stacked column; the shared part never fails on rank."""
+    kind = _lib.BORDERED_QR
+
+
 class LSMR(AbstractSolver):
     """LSMR(preconditioner!, P) (types.jl:82-86).
 
@@ -215,7 +225,8 @@ class BorderedBlockDiagonal:
     to back, then the ng border columns of m values each.
     On the device it becomes a CSC handle that knows its shape (lsq_blockdiag_bordered_create): LSMR() is the default solver,
     Cholesky() eliminates the locals block by block and factors the ng x ng Schur complement (nb + ng <= 64;
-    LevenbergMarquardt only), Schur() does the same for any ng (nb <= 64), QR() and BlockQR() are refused."""
+    LevenbergMarquardt only), Schur() does the same for any ng (nb <= 64), BorderedQR() solves the same damped problem by
+    Householder reflectors without forming J'J (nb <= 64, any ng), QR() and BlockQR() are refused."""
 
     def __init__(self, nblocks, mb, nb, ng, data=None):
         nblocks, mb, nb, ng = int(nblocks), int(mb), int(nb), int(ng)
@@ -301,6 +312,9 @@ BORDERED_DOGLEG_TEXT = ("Dogleg(Cholesky()) is not available on a bordered block
 SCHUR_HANDLE_TEXT = ("Schur() needs a BorderedBlockDiagonal Jacobian (got a %s of shape %s). Use Cholesky() or QR() on a dense "
                      "Jacobian, Cholesky() or BlockQR() on a BlockDiagonal one, LSMR() on a sparse one")
 SCHUR_NB_TEXT = "Schur() on a BorderedBlockDiagonal Jacobian needs nb <= 64 (got nb = %d, ng = %d). Use LSMR()"
+BORDERED_QR_HANDLE_TEXT = ("BorderedQR() needs a BorderedBlockDiagonal Jacobian (got a %s of shape %s). Use QR() on a dense "
+                           "Jacobian, BlockQR() on a BlockDiagonal one, LSMR() on a sparse one")
+BORDERED_QR_NB_TEXT = "BorderedQR() on a BorderedBlockDiagonal Jacobian needs nb <= 64 (got nb = %d, ng = %d). Use LSMR()"
 
 
 def _is_bordered(J):
@@ -320,6 +334,12 @@ def default_solver(solver, J):
             raise ArgumentError(_lib.EARG, SCHUR_HANDLE_TEXT % (type(J).__name__, tuple(getattr(J, "shape", ()))))
         if J.nb > 64:
             raise ArgumentError(_lib.EARG, SCHUR_NB_TEXT % (J.nb, J.ng))
+        return solver
+    if isinstance(solver, BorderedQR):
+        if not _is_bordered(J):
+            raise ArgumentError(_lib.EARG, BORDERED_QR_HANDLE_TEXT % (type(J).__name__, tuple(getattr(J, "shape", ()))))
+        if J.nb > 64:
+            raise ArgumentError(_lib.EARG, BORDERED_QR_NB_TEXT % (J.nb, J.ng))
         return solver
     if _is_bordered(J):
         if isinstance(solver, QR):
@@ -347,9 +367,9 @@ def default_solver(solver, J):
 
 
 def default_optimizer(optimizer, solver, J=None):
-    """types.jl:123-127.  On a BorderedBlockDiagonal J, Cholesky() and Schur() come with LevenbergMarquardt (Dogleg with either
-    does not exist there and is refused)."""
-    if isinstance(solver, Schur) or (_is_bordered(J) and isinstance(solver, Cholesky)):
+    """types.jl:123-127.  On a BorderedBlockDiagonal J, Cholesky(), Schur() and BorderedQR() come with LevenbergMarquardt
+    (Dogleg with any of them does not exist there and is refused)."""
+    if isinstance(solver, (Schur, BorderedQR)) or (_is_bordered(J) and isinstance(solver, Cholesky)):
         if isinstance(optimizer, Dogleg):
             raise ArgumentError(_lib.EARG, BORDERED_DOGLEG_TEXT)
         return LevenbergMarquardt(solver)
@@ -878,7 +898,7 @@ class AllocatedSolver:
             block_ranks = np.zeros(self.J.blockdiag_info()[0], dtype=np.int32)
             check(lib().lsq_solver_blockdiag_ranks(self.h, block_ranks.ctypes.data_as(_lib.c_ip)))
         return dict(blockdiag_path={0: None, 1: "batched-unpivoted", 2: "batched-pivoted", 3: "batched-qr",
-                                    4: "bordered-schur", 5: "bordered-schur-tiled"}[bpath.value],
+                                    4: "bordered-schur", 5: "bordered-schur-tiled", 6: "bordered-qr"}[bpath.value],
                     blockdiag_block=bblock.value, block_ranks=block_ranks,
                     lsmr_iter=it.value, lsmr_istop=st.value, qr_rank=rk.value,
                     lsmr_path={0: None, 1: "reference-order", 2: "four-launch", 3: "three-launch", 4: "general"}[lpath.value],
@@ -1717,6 +1737,10 @@ def _batched_arguments(J, optimizer, n, lower, upper):
         raise ArgumentError(_lib.EARG, "optimize_batched_: Schur() solves the one coupled system of a BorderedBlockDiagonal "
                                        "Jacobian, there is no trust region per block in it. Use optimize_ with "
                                        "LevenbergMarquardt(Schur())")
+    if isinstance(solver, BorderedQR):
+        raise ArgumentError(_lib.EARG, "optimize_batched_: BorderedQR() solves the one coupled system of a "
+                                       "BorderedBlockDiagonal Jacobian, there is no trust region per block in it. Use "
+                                       "optimize_ with LevenbergMarquardt(BorderedQR())")
     if isinstance(solver, LSMR):
         raise ArgumentError(_lib.EARG, "optimize_batched_: LSMR() is not available per block (an iterative solve per block "
                                        "is a different loop). Use Cholesky(), or optimize_ for one trust region over the "

@@ -458,6 +458,11 @@ extern "C" int lsq_optimize_batched(lsq_ctx *c, int optimizer, int solver_kind, 
                       "no trust region per block in it. Use lsq_optimize with LevenbergMarquardt");
         return LSQ_EARG;
     }
+    if (solver_kind == LSQ_BORDERED_QR) {
+        lsq_set_error("lsq_optimize_batched: BorderedQR() solves the one coupled system of a bordered block-diagonal Jacobian, "
+                      "there is no trust region per block in it. Use lsq_optimize with LevenbergMarquardt");
+        return LSQ_EARG;
+    }
     if (J->kind != LSQ_MAT_CSC || J->bd_blocks < 1) {
         lsq_set_error("lsq_optimize_batched: the Jacobian is not block-diagonal (lsq_blockdiag_create): one trust region per "
                       "block needs the block shape");

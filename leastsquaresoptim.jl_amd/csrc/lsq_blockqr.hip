@@ -24,6 +24,7 @@
 
 #include "lsq_solver.h"
 #include "lsq_laic1.h"
+#include "lsq_bq.h"      // bq_sync, bq_quad_sum, bq_larfg
 
 constexpr double BQ_MIN_DIAGONAL = 1e-6, BQ_MAX_DIAGONAL = 1e32;   // levenberg_marquardt.jl:85 (per-block damping, `delta`)
 
@@ -31,33 +32,6 @@ constexpr double BQ_MIN_DIAGONAL = 1e-6, BQ_MAX_DIAGONAL = 1e32;   // levenberg_
 // | vn1 vn2 (partial column norms) | dg (diag(J'J)) | sd (sqrt of the damping)
 __host__ __device__ static inline size_t bq_group_doubles(int nb, int H) {
     return (size_t)(nb | 1) * (nb + 1) + (size_t)(nb + 1) * (H + 1) + 4 * (size_t)nb;
-}
-
-template <int G>
-__device__ __forceinline__ void bq_sync() {
-    if (G == 4) __syncthreads();
-    else {      // one wavefront owns the block: order its own LDS traffic, nothing to wait for
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    }
-}
-
-__device__ __forceinline__ double bq_quad_sum(double v) {   // (p0 + p1) + (p2 + p3), the same bits in the four threads
-    v += __shfl_xor(v, 1);
-    v += __shfl_xor(v, 2);
-    return v;
-}
-
-// dlarfg on (alpha, x) with |x|^2 = s2: H = I - tau v v', v = (1, x * sc), H (alpha, x) = (beta, 0).  s2 is a plain sum of
-// squares (as in k_qrcp_solve), without dnrm2's scaling and dlarfg's safmin loop: columns whose entries leave about
-// 1e-150 .. 1e150 overflow or underflow here where LAPACK would not.
-__device__ __forceinline__ void bq_larfg(double alpha, double s2, double *tau, double *sc, double *beta) {
-    if (s2 == 0.0) { *tau = 0.0; *sc = 0.0; *beta = alpha; return; }
-    const double bt = -copysign(hypot(alpha, sqrt(s2)), alpha);
-    *tau = (bt - alpha) / bt;
-    *sc = 1.0 / (alpha - bt);
-    *beta = bt;
 }
 
 template <int G, int H>

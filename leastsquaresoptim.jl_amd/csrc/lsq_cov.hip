@@ -226,6 +226,12 @@ extern "C" int lsq_solver_covariance(lsq_solver *s, lsq_mat *J, const double *d_
                       "when nb + ng <= 64");
         return LSQ_EARG;
     }
+    if (s->kind == LSQ_BORDERED_QR) {
+        lsq_set_error("lsq_solver_covariance: not available on a BorderedQR() solver (a covariance from its factors is not "
+                      "built). Use lsq_sparse_covariance with an LSMR() solver on the same handle, or a Cholesky() solver "
+                      "when nb + ng <= 64");
+        return LSQ_EARG;
+    }
     if (s->kind != LSQ_CHOLESKY || (s->bd_blocks == 0 && s->br_blocks == 0)) {
         lsq_set_error("lsq_solver_covariance: needs a Cholesky() solver created on a block-diagonal (lsq_blockdiag_create) or "
                       "bordered block-diagonal (lsq_blockdiag_bordered_create) Jacobian (this solver's kind is %d)", s->kind);

@@ -139,7 +139,11 @@ struct lsq_solver {
     // d_chol.  lsq_sparse_covariance on an LSMR() solver (lsq_cov_sparse.hip), created on first use: m, n of this one, J'J.
     // Schur() on a bordered handle (lsq_schur.hip; br_blocks > 0, d_info and d_work as above), created with the solver: n = ng,
     // the Schur complement of the locals
+    // BorderedQR() on a bordered handle (lsq_borderedqr.hip; br_blocks > 0, d_info and d_work as above), created with the solver:
+    // a dense QR() solver (for_lm) with m rows and n = ng, and inner_J, the dense handle it solves on: a view of the
+    // transformed border inside d_work that owns nothing
     lsq_solver *inner = nullptr;
+    lsq_mat *inner_J = nullptr;
 };
 int lsq_tri_chol_solve(lsq_solver *s, const double *U, int n, double *d_bx);
 int lsq_tri_chol_fwd_operands(lsq_solver *s, int n, double **z, unsigned long long **slot, unsigned long long *epoch, int **err);
@@ -279,6 +283,9 @@ int lsq_bordered_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double
 // implemented in lsq_schur.hip
 int lsq_schur_solver_alloc(lsq_solver *s, const lsq_mat *J);
 int lsq_schur_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);
+// implemented in lsq_borderedqr.hip
+int lsq_borderedqr_solver_alloc(lsq_solver *s, const lsq_mat *J);
+int lsq_borderedqr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);
 // implemented in lsq_blockqr.hip
 int lsq_blockqr_solver_alloc(lsq_solver *s, const lsq_mat *J);
 int lsq_blockqr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);

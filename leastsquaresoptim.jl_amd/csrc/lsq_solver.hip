@@ -27,7 +27,7 @@ extern "C" int lsq_solver_create(lsq_ctx *c, lsq_mat *J, int kind, int for_lm, l
     s->m = J->m;
     s->n = J->n;
     int st = (kind == LSQ_LSMR) ? lsq_lsmr_alloc(s) : (kind == LSQ_BLOCK_QR) ? lsq_blockqr_solver_alloc(s, J)
-             : (kind == LSQ_SCHUR) ? lsq_schur_solver_alloc(s, J)
+             : (kind == LSQ_SCHUR) ? lsq_schur_solver_alloc(s, J) : (kind == LSQ_BORDERED_QR) ? lsq_borderedqr_solver_alloc(s, J)
              : blockdiag ? lsq_blockdiag_solver_alloc(s, J) : bordered ? lsq_bordered_solver_alloc(s, J) : lsq_dense_solver_alloc(s);
     if (st != LSQ_OK) {
         delete s;
@@ -43,10 +43,11 @@ extern "C" int lsq_solver_destroy(lsq_solver *s) {
     if (s->kind == LSQ_LSMR) lsq_lsmr_free(s);
     else lsq_dense_solver_free(s);     // (also the block-diagonal solvers: all they own is d_info, freed there)
     hipFree(s->d_cov_info); hipFree(s->d_cov_buf);     // lsq_solver_covariance
-    if (s->inner) {                                // lsq_sparse_covariance, Schur()
+    if (s->inner) {                                // lsq_sparse_covariance, Schur(), BorderedQR()
         lsq_dense_solver_free(s->inner);
         delete s->inner;
     }
+    delete s->inner_J;                             // (a view: its values belong to d_work)
     delete s;
     return LSQ_OK;
 }
@@ -82,6 +83,7 @@ extern "C" int lsq_ldiv(lsq_solver *s, lsq_mat *J, const double *y, double *x, i
         return s->bd_blocks ? lsq_blockdiag_solve(s, J, y, nullptr, x, nmul) : lsq_cholesky_solve(s, J, y, nullptr, x, nmul);
     case LSQ_BLOCK_QR: return lsq_blockqr_solve(s, J, y, nullptr, x, nmul);
     case LSQ_SCHUR: return lsq_schur_solve(s, J, y, nullptr, x, nmul);             // (refused: LM only)
+    case LSQ_BORDERED_QR: return lsq_borderedqr_solve(s, J, y, nullptr, x, nmul);  // (refused: LM only)
     default: return lsq_qr_solve(s, J, y, nullptr, x, nmul);
     }
 }
@@ -96,6 +98,7 @@ extern "C" int lsq_ldiv_damped(lsq_solver *s, lsq_mat *J, const double *y, doubl
         return s->bd_blocks ? lsq_blockdiag_solve(s, J, y, damp, x, nmul) : lsq_cholesky_solve(s, J, y, damp, x, nmul);
     case LSQ_BLOCK_QR: return lsq_blockqr_solve(s, J, y, damp, x, nmul);
     case LSQ_SCHUR: return lsq_schur_solve(s, J, y, damp, x, nmul);
+    case LSQ_BORDERED_QR: return lsq_borderedqr_solve(s, J, y, damp, x, nmul);
     default: return lsq_qr_solve(s, J, y, damp, x, nmul);
     }
 }
@@ -113,12 +116,12 @@ extern "C" int lsq_solver_set_preconditioner(lsq_solver *s, lsq_precond_callback
 
 extern "C" int lsq_solver_qr_panel(const lsq_solver *s, int *kind) {
     if (!s || !kind) { lsq_set_error("lsq_solver_qr_panel: null argument"); return LSQ_EARG; }
-    *kind = s->last_qr_panel;
+    *kind = s->kind == LSQ_BORDERED_QR ? s->inner->last_qr_panel : s->last_qr_panel;   // (BorderedQR(): the inner QR()'s)
     return LSQ_OK;
 }
 extern "C" int lsq_solver_qr_path(const lsq_solver *s, int *path) {
     if (!s || !path) { lsq_set_error("lsq_solver_qr_path: null argument"); return LSQ_EARG; }
-    *path = s->last_qr_path;
+    *path = s->kind == LSQ_BORDERED_QR ? s->inner->last_qr_path : s->last_qr_path;
     return LSQ_OK;
 }
 
@@ -129,7 +132,13 @@ extern "C" int lsq_solver_stats(const lsq_solver *s, int h_giveups[4], int h_pau
         if (h_giveups) h_giveups[i] = fb[i]->giveups;
         if (h_paused) h_paused[i] = fb[i]->cooldown;
     }
-    if (s->inner) {      // an LSMR() solver after lsq_sparse_covariance, a Schur() solver: the factorisation of its inner dense solver
+    if (s->kind == LSQ_BORDERED_QR) {      // the inner QR()'s panel exchange and CholeskyQR2 panels
+        for (int i = 2; i < 4; ++i) {
+            const LsqFallback &fi = i == 2 ? s->inner->fb_qrx : s->inner->fb_cholqr;
+            if (h_giveups) h_giveups[i] += fi.giveups;
+            if (h_paused) h_paused[i] += fi.cooldown;
+        }
+    } else if (s->inner) {      // an LSMR() solver after lsq_sparse_covariance, a Schur() solver: the factorisation of its inner dense solver
         if (h_giveups) h_giveups[0] += s->inner->fb_tiles.giveups;
         if (h_paused) h_paused[0] += s->inner->fb_tiles.cooldown;
     }
@@ -156,6 +165,10 @@ extern "C" int lsq_solver_info(const lsq_solver *s, int *iter, int *istop, int *
         if (s->kind == LSQ_QR && s->d_info) {
             LSQ_HIP(hipStreamSynchronize(s->ctx->stream));
             LSQ_HIP(hipMemcpy(rank, s->d_info, sizeof(int), hipMemcpyDeviceToHost));
+        } else if (s->kind == LSQ_BORDERED_QR && s->last_bd_path == 6) {   // the locals have full rank or the solve failed
+            int inner_rank = 0;
+            LSQ_TRY(lsq_solver_info(s->inner, nullptr, nullptr, &inner_rank));
+            *rank = s->br_blocks * s->br_nb + inner_rank;
         } else if (s->kind == LSQ_BLOCK_QR && s->bq_solved) {    // the sum of the block ranks
             std::vector<int> hr((size_t)s->bd_blocks);
             LSQ_TRY(lsq_solver_blockdiag_ranks(s, hr.data()));
