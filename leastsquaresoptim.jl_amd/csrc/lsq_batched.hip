@@ -209,9 +209,11 @@ k_bt_step(int B, int mb, int nb, BtDev s, bool qr, const double *__restrict__ va
             if (fresh) s.mcalls[b] += 3;
         }
     }
-    if (lo && in) d = fmin(d, xv - lo[j]);                                        // levenberg_marquardt.jl:89-98
-    if (hi && in) d = fmax(d, xv - hi[j]);
-    const double maxdx = wave_max(fabs(d));
+    // levenberg_marquardt.jl:89-98.  Julia's min / max propagate NaN from EITHER argument (fmin / fmax drop it): a NaN step
+    // component must stay NaN so that the block's trial point is non-finite, as k_box_clip keeps it for a single fit
+    if (lo && in) { const double a = xv - lo[j]; d = (d != d || a != a) ? d + a : (d < a ? d : a); }
+    if (hi && in) { const double a = xv - hi[j]; d = (d != d || a != a) ? d + a : (d > a ? d : a); }
+    const double maxdx = wave_max(d != d ? INFINITY : fabs(d));     // maximum(abs, dx): a NaN fails "<= x_tol", as in lsq_vec.hip
     if (in) {
         dx[j] = d;
         xt[j] = xv + -1.0 * d;                                                    // axpy!(-1, dx, x)

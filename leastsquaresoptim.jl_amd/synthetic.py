@@ -158,7 +158,8 @@ class TanhProblem:
 
     def optimize(self, optimizer_kind, solver_kind, x_tol=1e-8, f_tol=1e-8, g_tol=1e-8, iterations=1000,
                  delta=None, trace=False, allreduce=None, fetch_x=True, row_allreduce=None, row_allreduce_user=None,
-                 global_rows=0):
+                 global_rows=0, lower=None, upper=None):
+        """lower / upper: box bounds of length n (host arrays), as optimize_ takes them; None = unbounded."""
         # (the handle wrapper and the two callback pointers are made once per problem: a solve of the bench schedule takes 2 ms,
         #  and tens of microseconds of interpreter work per call showed in its timeline)
         if self._Jd is None:
@@ -168,7 +169,7 @@ class TanhProblem:
         Jd = self._Jd
         st, res, tr = _run_native(self.ctx, optimizer_kind, solver_kind, Jd, self.x, self.fcur,
                                   self._fg[0], self._fg[1], self.model, x_tol, f_tol, g_tol,
-                                  iterations, delta, None, None, trace, self.n, allreduce=allreduce,
+                                  iterations, delta, lower, upper, trace, self.n, allreduce=allreduce,
                                   row_allreduce=row_allreduce, row_allreduce_user=row_allreduce_user, global_rows=global_rows)
         check(st)
         r = LeastSquaresResult()

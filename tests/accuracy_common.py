@@ -65,6 +65,14 @@ def lsmr_bound(e_ref, n, iters):
     return FACTOR * max(float(e_ref), min(max(16, n), FLOOR_CAP) * UNIT * iters)
 
 
+def trajectory_bound(e_ref, k, iteration, cond=1.0):
+    """The same rule for a quantity of outer iteration `iteration` (counted from 1) of a trust-region run
+    (tests/test_v_gpu_trust_region.py): the floor is that of a sum of length k, once per iteration the run has behind it, times
+    `cond`, the condition number of the quantity with respect to those sums where it is not 1 (rho: ssr / pred_red, the
+    quotient of two differences of sums of squares; the gradient norm: max |J|'|f| / max |J'f|)."""
+    return FACTOR * max(float(e_ref), min(max(16, k), FLOOR_CAP) * UNIT * iteration * max(1.0, float(cond)))
+
+
 def accepted(e_dev, e_ref, k):
     return bool(np.isfinite(e_dev)) and float(e_dev) <= bound(e_ref, k)
 

@@ -73,7 +73,10 @@ def ldiv_lsmr(J, y, damp=None, dtype=np.float64, iters=None, wide_sums=False, ma
     if wide_sums:
         matvec, sumsq_cols = _wide(matvec), _wide(sumsq_cols)
         nrm = lambda v: np.sqrt(_wide(lambda t: t @ t)(v))  # noqa: E731
-    J = np.asarray(J, dtype=T)
+    if hasattr(J, "colsumabs2"):       # an operator with @, .T, .shape (tests/trust_region_reference.py: Band), already in T
+        sumsq_cols = lambda A: A.colsumabs2()  # noqa: E731
+    else:
+        J = np.asarray(J, dtype=T)
     y = np.asarray(y, dtype=T)
     m, n = J.shape
     damped = damp is not None
