@@ -134,7 +134,8 @@ int lsq_mat_blockdiag_info(const lsq_mat *J, int *nblocks, int *mb, int *nb);
  * the block), lsq_solver_qr_path / lsq_solver_qr_panel the inner solver's values, lsq_solver_stats (indices 2 and 3) its
  * give-ups.  LSQ_EARG: any other handle, nb > 64, for_lm = 0 / lsq_ldiv / Dogleg (LSQ_CHOLESKY's text, for the same reason),
  * lsq_optimize_batched, lsq_solver_covariance / lsq_dense_covariance / lsq_dense_qr_covariance / lsq_sparse_covariance, a
- * handle of another shape than the solver was created for. */
+ * handle of another shape than the solver was created for.  Its covariance, cross-covariances included, is
+ * lsq_bordered_qr_covariance below. */
 int lsq_blockdiag_bordered_create(lsq_ctx *ctx, int nblocks, int mb, int nb, int ng, lsq_mat **out);
 /* all 0 for any other handle */
 int lsq_mat_bordered_info(const lsq_mat *J, int *nblocks, int *mb, int *nb, int *ng);
@@ -389,6 +390,36 @@ int lsq_dense_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double *d
  * is split into other slabs).  Waits where the solve waits (the certificate's copy) and once more, for the rank and s^2, which
  * are read back to back; the last two launches are stream-ordered behind that. */
 int lsq_dense_qr_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double *d_cov, double *d_stderr, int *h_info);
+/* The same for a bordered block-diagonal Jacobian J = [blkdiag(J_1 .. J_B) | C] (lsq_blockdiag_bordered_create), from the
+ * factor of LSQ_BORDERED_QR, with the local-shared cross-covariances: Cov = s^2 inv(J'J) with ONE variance
+ * s^2 = sum(f.^2) / (m - n), m = B*mb, n = B*nb + ng.  Neither J'J nor any part of it is formed, so the condition number is not
+ * squared.  `s` is an LSQ_BORDERED_QR solver created on the handle J (nb <= 64, any ng >= 1, for_lm = 1).  A column-scaled
+ * handle means J S.  No damping is involved; J and d_f are not written.
+ *   d_f: NULL (s^2 = 1) or the residual (m doubles, device), summed through lsq_sumsq.
+ *   d_cov: NULL or B*nb*nb + ng*ng doubles in lsq_solver_covariance's layout for this handle: the B local blocks, then the
+ *   shared block; every block is written with both triangles holding the same bits.
+ *   d_stderr: NULL or n doubles in parameter order: the same bits whichever of d_cov / d_cross is asked for as well.  They agree
+ *   with sqrt(diag(cov)) to rounding only.
+ *   d_cross: NULL or (B*nb) x ng doubles, column-major with leading dimension B*nb: row b*nb + i, column j is
+ *   Cov(local i of block b, shared j) -- the off-diagonal panel of the full covariance matrix in parameter order.
+ *   h_info: NULL or 2 ints.  h_info[0]: 0, or the 1-based stacked column b*nb + k at which some R_b has a zero or non-finite
+ *   diagonal entry (the lowest wins: the column lsq_ldiv_damped names); h_info[1]: the rank the inner QR() decided.
+ * With zero damping the elimination of LSQ_BORDERED_QR leaves per block Q_b'[J_b C_b] = [R_b W_b; 0 F_b].  Cgg = inv(F'F) is
+ * lsq_dense_qr_covariance on the solver's own inner QR() (every factorisation path and retry it has; an ng x ng buffer owned
+ * by the solver, allocated at the first call with m zeros for the elimination's damping and right-hand side); then
+ * T_b = inv(R_b) W_b in place of W, the tall product P = T Cgg ((B*nb) x ng times ng x ng, on the fp64 matrix unit), and per
+ * block Cov_bb = s^2 (inv(R_b) inv(R_b)' + P_b T_b'); Cov_gg = s^2 Cgg, Cov_bg = -s^2 P_b.  P stands in the solver's own
+ * workspace (the place of F): no output-sized buffer is allocated that the caller did not ask for.
+ * A failing local column: LSQ_ERANK with LSQ_BORDERED_QR's message and column.  An inner rank < ng: LSQ_ERANK with a message
+ * that states rank and ng.  The outputs are then unspecified; the solver stays usable for solves and further covariances, and
+ * a solve after a covariance has the bits of a solve without one.  A pseudo-inverse is not offered.
+ * LSQ_EARG, each with a message that names the alternative: a solver of another kind; a handle that is not bordered; a shape
+ * other than the solver's; m < n; d_f with m <= n; d_cov, d_stderr and d_cross all NULL.
+ * Waits where the inner QR() waits and once more, for the locals' verdict, the rank and s^2, which are read back to back; the
+ * launches after that are stream-ordered.  No floating-point atomics, no workgroup waits for another, every sum has a fixed
+ * association: the same bits on every run, on a second solver and under lsq_debug_set(serial = 1). */
+int lsq_bordered_qr_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double *d_cov, double *d_stderr, double *d_cross,
+                               int *h_info);
 /* G = J'J (+ diag(d_damp)) of a sparse Jacobian as a dense matrix, formed on the device without densifying J (k_sp_gram,
  * lsq_cov_sparse.hip).  J: any LSQ_MAT_CSC handle -- lsq_csc_create, lsq_blockdiag_create, lsq_blockdiag_bordered_create -- at
  * the values it holds; a column-scaled handle means J S.  d_damp: NULL or n doubles added to the diagonal.  d_G: n x n doubles,

@@ -4,7 +4,7 @@ from . import _lib
 from ._lib import (ArgumentError, DimensionMismatch, HipError, IsFiniteException, LsqError,
                    PeerAborted, PosDefException, RankDeficientException, build, declared_symbols, lib)
 from .api import (axpy_, box_clip_, clamp_, copyto_, ediv_, fill_, first_nonfinite, rmul_, vsum,
-                  AllocatedSolver, BatchedResult, BlockDiagonal, Covariance, covariance, DenseCovariance, dense_covariance, dense_qr_covariance, sparse_covariance, sparse_gram, BlockQR, BorderedBlockDiagonal, BorderedQR, Cholesky, Schur, Context, PinnedBuffer, DeviceMatrix, DeviceOperator, DeviceVector, Dogleg, LSMR,
+                  AllocatedSolver, BatchedResult, BlockDiagonal, Covariance, covariance, DenseCovariance, dense_covariance, dense_qr_covariance, sparse_covariance, BorderedCovariance, bordered_qr_covariance, sparse_gram, BlockQR, BorderedBlockDiagonal, BorderedQR, Cholesky, Schur, Context, PinnedBuffer, DeviceMatrix, DeviceOperator, DeviceVector, Dogleg, LSMR,
                   LeastSquaresProblem, LeastSquaresProblemAllocated, LeastSquaresResult, LevenbergMarquardt, OptimizationState, QR,
                   colsumabs2_, rowsumabs2_, converged, default_context, default_optimizer, default_solver,
                   fd_jacobian_, greedy_colouring, maxabs, maxabs_projected_gradient, mul_, norm, optimize, optimize_, optimize_batched_, set_exact, debug_set, debug_get, sumsq, wdot,

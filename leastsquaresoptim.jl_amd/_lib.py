@@ -165,6 +165,7 @@ def lib():
         "lsq_solver_covariance": (i, [vp, vp, vp, vp, vp, c_ip]),
         "lsq_dense_covariance": (i, [vp, vp, vp, vp, vp, c_ip]),
         "lsq_dense_qr_covariance": (i, [vp, vp, vp, vp, vp, c_ip]),
+        "lsq_bordered_qr_covariance": (i, [vp, vp, vp, vp, vp, vp, c_ip]),
         "lsq_sparse_gram": (i, [vp, vp, vp]),
         "lsq_sparse_covariance": (i, [vp, vp, vp, vp, vp, c_ip]),
         "lsq_solver_stats": (i, [vp, c_ip, c_ip]),

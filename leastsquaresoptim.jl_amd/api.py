@@ -961,6 +961,23 @@ class AllocatedSolver:
         return DenseCovariance(J.n, dcov.get() if cov else None, dse.get() if stderr else None,
                                chol_path=self.info()["chol_path"])
 
+    def bordered_qr_covariance(self, f=None, cov=True, stderr=True, cross=False):
+        """lsq_bordered_qr_covariance at the values the bordered J holds now, from the factor of this BorderedQR() solver (J'J is
+        not formed): a BorderedCovariance.  `f`: None (the unscaled inv(J'J)), or the residual (DeviceVector or m host values):
+        one variance s^2 = sum(f.^2) / (m - n).  cross=True: the (B nb) x ng local-shared cross-covariances as well.  A zero or
+        non-finite local column, or a rank-deficient border, raises RankDeficientException."""
+        J = self.J
+        B, _, nb, ng = J.bordered if J.bordered is not None else (0, 0, 0, 0)   # (any other handle is refused by the library)
+        df = f if (f is None or hasattr(f, "ptr")) else DeviceVector(J.ctx, J.m, f)
+        dcov = DeviceVector(J.ctx, B * nb * nb + ng * ng) if cov else None
+        dse = DeviceVector(J.ctx, J.n) if stderr else None
+        dcr = DeviceVector(J.ctx, B * nb * ng) if cross else None
+        info = np.zeros(2, dtype=np.int32)
+        check(lib().lsq_bordered_qr_covariance(self.h, J.h, _ptr(df), _ptr(dcov), _ptr(dse), _ptr(dcr),
+                                               info.ctypes.data_as(_lib.c_ip)))
+        return BorderedCovariance(B, nb, ng, dcov.get() if cov else None, dse.get() if stderr else None,
+                                  dcr.get() if cross else None, rank=int(info[1]))
+
     def stats(self):
         """lsq_solver_stats: give-ups of the co-residency fast paths and how many solves each stays paused."""
         g, p = (C.c_int * 4)(), (C.c_int * 4)()
@@ -1018,6 +1035,57 @@ def covariance(Jd, f=None, stderr=True):
     sv = AllocatedSolver(Jd, Cholesky(), for_lm=True)
     try:
         return sv.covariance(f=f, stderr=stderr)
+    finally:
+        sv.free()
+
+
+class BorderedCovariance(Covariance):
+    """What lsq_bordered_qr_covariance returns, on the host: a Covariance (`.block(b)`, `.shared`, `.stderr`; `.cov` is None
+    when it was not asked for, `.info` is None) with `.cross`, the (B nb) x ng local-shared cross-covariances -- the
+    off-diagonal panel of the full covariance matrix in parameter order -- or None, `.cross_block(b)` its nb x ng rows of
+    block b (a view), and `.rank`, the rank the inner QR() decided for the shared columns."""
+
+    def __init__(self, nblocks, nb, ng, cov=None, stderr=None, cross=None, rank=None):
+        size = int(nblocks) * int(nb) * int(nb) + int(ng) * int(ng)
+        super().__init__(nblocks, nb, ng, np.zeros(size) if cov is None else cov, stderr)
+        if cov is None:
+            self.cov = None
+        self.rank = rank
+        if cross is None:
+            self.cross = None
+        else:
+            cross = np.asarray(cross, dtype=np.float64)
+            if cross.size != self.nblocks * self.nb * self.ng:
+                raise DimensionMismatch(_lib.EDIM, "cross-covariance of %d x %d locals and %d shared parameters has %d entries, "
+                                        "got %s" % (self.nblocks, self.nb, self.ng, self.nblocks * self.nb * self.ng, cross.shape))
+            self.cross = cross.reshape((self.nblocks * self.nb, self.ng), order="F")
+
+    def block(self, b):
+        if self.cov is None:
+            raise ValueError("the covariance blocks were not asked for (cov=False)")
+        return super().block(b)
+
+    @property
+    def shared(self):
+        if self.cov is None:
+            return None
+        return Covariance.shared.fget(self)
+
+    def cross_block(self, b):
+        if self.cross is None:
+            raise ValueError("the cross-covariances were not asked for (cross=False)")
+        if not 0 <= b < self.nblocks:
+            raise IndexError("block %d of %d" % (b, self.nblocks))
+        return self.cross[b * self.nb:(b + 1) * self.nb]
+
+
+def bordered_qr_covariance(Jd, f=None, cov=True, stderr=True, cross=False):
+    """Covariance of the parameters of a bordered block-diagonal DeviceMatrix at the values it holds, without squaring the
+    condition number and for any ng: creates a BorderedQR() solver on it, calls AllocatedSolver.bordered_qr_covariance and frees
+    the solver."""
+    sv = AllocatedSolver(Jd, BorderedQR(), for_lm=True)
+    try:
+        return sv.bordered_qr_covariance(f=f, cov=cov, stderr=stderr, cross=cross)
     finally:
         sv.free()
 

@@ -376,6 +376,23 @@ static int bdq_factor(lsq_ctx *c, lsq_solver *s, lsq_mat *J, const double *d_y, 
     return LSQ_OK;
 }
 
+// the elimination of the locals, enqueued: k_bdq_init, k_bdq_factor, k_bdq_apply (also lsq_bordered_qr_covariance,
+// lsq_cov_bordered.hip, with zeros for d_y and d_damp).  view (optional): where R, W and F stand in s->d_work
+int lsq_borderedqr_eliminate(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, LsqBdqView *view) {
+    lsq_ctx *c = s->ctx;
+    const int nb = s->br_nb;
+    const BdqLayout l = bdq_layout(s->br_blocks, s->br_mb, nb, s->br_ng);
+    LSQ_LAUNCH(k_bdq_init, dim3(1), dim3(64), 0, c->stream, s->d_info);
+    if (nb > 16) LSQ_TRY(l.H == 64 ? (bdq_factor<4, 64>(c, s, J, d_y, d_damp, l)) : (bdq_factor<4, 32>(c, s, J, d_y, d_damp, l)));
+    else LSQ_TRY(l.H == 64 ? (bdq_factor<1, 64>(c, s, J, d_y, d_damp, l)) : (bdq_factor<1, 32>(c, s, J, d_y, d_damp, l)));
+    if (view) {
+        view->R = s->d_work + l.R;
+        view->W = s->d_work + l.W;
+        view->F = s->d_work + l.F;
+    }
+    return LSQ_OK;
+}
+
 int lsq_borderedqr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul) {
     lsq_ctx *c = s->ctx;
     if (!d_damp) return lsq_bordered_refuse_dogleg();
@@ -392,9 +409,7 @@ int lsq_borderedqr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const dou
     const BdqLayout l = bdq_layout(B, mb, nb, ng);
     double *wk = s->d_work;
     double *xg = d_x + (size_t)B * nb;
-    LSQ_LAUNCH(k_bdq_init, dim3(1), dim3(64), 0, c->stream, s->d_info);
-    if (nb > 16) LSQ_TRY(l.H == 64 ? (bdq_factor<4, 64>(c, s, J, d_y, d_damp, l)) : (bdq_factor<4, 32>(c, s, J, d_y, d_damp, l)));
-    else LSQ_TRY(l.H == 64 ? (bdq_factor<1, 64>(c, s, J, d_y, d_damp, l)) : (bdq_factor<1, 32>(c, s, J, d_y, d_damp, l)));
+    LSQ_TRY(lsq_borderedqr_eliminate(s, J, d_y, d_damp, nullptr));
     // min || [F; diag(sqrt(damp_g))] x_g - [r; 0] ||: the inner QR()'s damped solve, its rank decision and its retries
     LSQ_TRY(lsq_qr_solve(s->inner, s->inner_J, wk + l.r, d_damp + (size_t)B * nb, xg, nullptr));
     const size_t lds_back = ((size_t)nb * (nb | 1) + 256) * sizeof(double);

@@ -234,6 +234,53 @@ extern "C" int lsq_dense_covariance(lsq_solver *s, lsq_mat *J, const double *d_f
 //   one-stage (1): R at the top of s->d_qr, leading dimension M: k_cov_tri_gather into s->d_T, then lsq_tri_inv_enqueue
 // and on the pivoted ones k_cov_xxt<true> / k_cov_stderr<true> un-permute on the way out.
 // ---------------------------------------------------------------------------------------------
+// The two halves of lsq_dense_qr_covariance around its wait (also lsq_bordered_qr_covariance, lsq_cov_bordered.hip, on the inner
+// QR() of a BorderedQR() solver, which reads the rank beside its own verdict).  Everything in front of the wait, enqueued: the
+// solve on zeros and, off the certified path, the inverse of the pivoted triangle; X = inv(R), jp = the pivots or nullptr
+int lsq_dense_qr_cov_factor(lsq_solver *s, lsq_mat *J, const double **Xout, const int **jpout) {
+    lsq_ctx *c = s->ctx;
+    const int m = J->m, n = J->n;
+    // zeros (the right-hand side, m; the damping of a for_lm solver, n <= m) | the solve's x, discarded (n)
+    if (!s->d_cov_buf) {
+        LSQ_HIP(hipMalloc(&s->d_cov_buf, ((size_t)m + n + 8) * sizeof(double)));
+        LSQ_HIP(hipMemsetAsync(s->d_cov_buf, 0, (size_t)m * sizeof(double), c->stream));
+    }
+    const double *zero = s->d_cov_buf;
+    LSQ_TRY(lsq_qr_solve(s, J, zero, s->for_lm ? zero : nullptr, s->d_cov_buf + m, nullptr));
+    const double *X = s->qr_X;
+    const int *jp = nullptr;
+    if (s->last_qr_path != 3 || !X) {
+        const double *U = s->qr_R;
+        if (s->qr_ldr != n) {
+            const long long tot = (long long)n * n;
+            const int g = (int)std::min<long long>((tot + 255) / 256, (long long)c->num_cus * 8);
+            LSQ_LAUNCH(k_cov_tri_gather, dim3(g), dim3(256), 0, c->stream, U, s->qr_ldr, n, s->d_T);
+            U = s->d_T;
+        }
+        LSQ_TRY(lsq_tri_inv_enqueue(s, U, n));
+        X = s->tri_X;
+        jp = (const int *)s->d_tau;
+    }
+    *Xout = X;
+    *jpout = jp;
+    return LSQ_OK;
+}
+
+// ... and behind it, once the rank is known to be n: s2 P X X' P' into d_cov, the standard errors into d_stderr (either may be null)
+int lsq_dense_qr_cov_finish(lsq_solver *s, int n, const double *X, const int *jp, double s2, double *d_cov, double *d_stderr) {
+    lsq_ctx *c = s->ctx;
+    const int nt = lsq_div_up(n, CX_T);
+    if (jp) {
+        if (d_cov) LSQ_LAUNCH(k_cov_xxt<true>, dim3(nt * (nt + 1) / 2), dim3(256), 0, c->stream, X, n, s2, d_cov, jp);
+        if (d_stderr) LSQ_LAUNCH(k_cov_stderr<true>, dim3(lsq_div_up(n, 4)), dim3(256), 0, c->stream, X, n, sqrt(s2), d_stderr, jp);
+    } else {
+        if (d_cov) LSQ_LAUNCH(k_cov_xxt<false>, dim3(nt * (nt + 1) / 2), dim3(256), 0, c->stream, X, n, s2, d_cov, jp);
+        if (d_stderr) LSQ_LAUNCH(k_cov_stderr<false>, dim3(lsq_div_up(n, 4)), dim3(256), 0, c->stream, X, n, sqrt(s2), d_stderr, jp);
+    }
+    LSQ_HIP(hipGetLastError());
+    return LSQ_OK;
+}
+
 extern "C" int lsq_dense_qr_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double *d_cov, double *d_stderr,
                                        int *h_info) {
     LSQ_RANGE("lsq_dense_qr_covariance");
@@ -269,27 +316,9 @@ extern "C" int lsq_dense_qr_covariance(lsq_solver *s, lsq_mat *J, const double *
     if (n <= 0) return LSQ_OK;
     lsq_ctx *c = s->ctx;
     LSQ_HIP(hipSetDevice(c->device));
-    // zeros (the right-hand side, m; the damping of a for_lm solver, n <= m) | the solve's x, discarded (n)
-    if (!s->d_cov_buf) {
-        LSQ_HIP(hipMalloc(&s->d_cov_buf, ((size_t)m + n + 8) * sizeof(double)));
-        LSQ_HIP(hipMemsetAsync(s->d_cov_buf, 0, (size_t)m * sizeof(double), c->stream));
-    }
-    const double *zero = s->d_cov_buf;
-    LSQ_TRY(lsq_qr_solve(s, J, zero, s->for_lm ? zero : nullptr, s->d_cov_buf + m, nullptr));
-    const double *X = s->qr_X;
+    const double *X = nullptr;
     const int *jp = nullptr;
-    if (s->last_qr_path != 3 || !X) {
-        const double *U = s->qr_R;
-        if (s->qr_ldr != n) {
-            const long long tot = (long long)n * n;
-            const int g = (int)std::min<long long>((tot + 255) / 256, (long long)c->num_cus * 8);
-            LSQ_LAUNCH(k_cov_tri_gather, dim3(g), dim3(256), 0, c->stream, U, s->qr_ldr, n, s->d_T);
-            U = s->d_T;
-        }
-        LSQ_TRY(lsq_tri_inv_enqueue(s, U, n));
-        X = s->tri_X;
-        jp = (const int *)s->d_tau;
-    }
+    LSQ_TRY(lsq_dense_qr_cov_factor(s, J, &X, &jp));
     // the one wait beyond the solve's own: the variance and, behind it, the rank decision of the solve
     double ssq = 0.0;
     int st4[4] = {0, 0, 0, 0};
@@ -304,14 +333,5 @@ extern "C" int lsq_dense_qr_covariance(lsq_solver *s, lsq_mat *J, const double *
         return LSQ_ERANK;
     }
     const double s2 = d_f ? ssq / (double)(m - n) : 1.0;
-    const int nt = lsq_div_up(n, CX_T);
-    if (jp) {
-        if (d_cov) LSQ_LAUNCH(k_cov_xxt<true>, dim3(nt * (nt + 1) / 2), dim3(256), 0, c->stream, X, n, s2, d_cov, jp);
-        if (d_stderr) LSQ_LAUNCH(k_cov_stderr<true>, dim3(lsq_div_up(n, 4)), dim3(256), 0, c->stream, X, n, sqrt(s2), d_stderr, jp);
-    } else {
-        if (d_cov) LSQ_LAUNCH(k_cov_xxt<false>, dim3(nt * (nt + 1) / 2), dim3(256), 0, c->stream, X, n, s2, d_cov, jp);
-        if (d_stderr) LSQ_LAUNCH(k_cov_stderr<false>, dim3(lsq_div_up(n, 4)), dim3(256), 0, c->stream, X, n, sqrt(s2), d_stderr, jp);
-    }
-    LSQ_HIP(hipGetLastError());
-    return LSQ_OK;
+    return lsq_dense_qr_cov_finish(s, n, X, jp, s2, d_cov, d_stderr);
 }

@@ -133,6 +133,7 @@ struct lsq_solver {
     int br_blocks = 0, br_mb = 0, br_nb = 0, br_ng = 0;
     // --- lsq_solver_covariance on either (lsq_cov.hip, lsq_bordered.hip), allocated on first use: the per-block verdicts;
     // bordered: zeros (the damping and right-hand side of the elimination) followed by the ng x ng block of the shared parameters
+    // (the same on a BorderedQR() solver: lsq_bordered_qr_covariance, lsq_cov_bordered.hip)
     int *d_cov_info = nullptr;
     double *d_cov_buf = nullptr;
     // --- a dense Cholesky() solver (lsq_dense_solver_alloc) owned by this one, factoring a Gram matrix that is written into its
@@ -286,6 +287,11 @@ int lsq_schur_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *
 // implemented in lsq_borderedqr.hip
 int lsq_borderedqr_solver_alloc(lsq_solver *s, const lsq_mat *J);
 int lsq_borderedqr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);
+// implemented in lsq_cov_dense.hip: lsq_dense_qr_covariance in front of and behind its wait for the rank (s->d_info[0])
+int lsq_dense_qr_cov_factor(lsq_solver *s, lsq_mat *J, const double **X, const int **jp);
+int lsq_dense_qr_cov_finish(lsq_solver *s, int n, const double *X, const int *jp, double s2, double *d_cov, double *d_stderr);
+struct LsqBdqView { double *R, *W, *F; };     // R_b (B nb x nb, rows) | W ((B nb) x ng, column-major) | F ((B mb) x ng) in d_work
+int lsq_borderedqr_eliminate(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, LsqBdqView *view);
 // implemented in lsq_blockqr.hip
 int lsq_blockqr_solver_alloc(lsq_solver *s, const lsq_mat *J);
 int lsq_blockqr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);

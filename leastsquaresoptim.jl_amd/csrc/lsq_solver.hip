@@ -44,6 +44,7 @@ extern "C" int lsq_solver_destroy(lsq_solver *s) {
     else lsq_dense_solver_free(s);     // (also the block-diagonal solvers: all they own is d_info, freed there)
     hipFree(s->d_cov_info); hipFree(s->d_cov_buf);     // lsq_solver_covariance
     if (s->inner) {                                // lsq_sparse_covariance, Schur(), BorderedQR()
+        hipFree(s->inner->d_cov_buf);              // (lsq_bordered_qr_covariance: the inner QR()'s zero right-hand side)
         lsq_dense_solver_free(s->inner);
         delete s->inner;
     }
