@@ -157,8 +157,8 @@ double *lsq_mat_values(lsq_mat *J);
  * FRESHNESS CONTRACT.  A handle keeps its values in several layouts (CSC order, row and column mirrors or sliced layouts, the
  * stored V of a multiplied-out column scale, the dense buffer), and which of them is the authority changes with the last
  * mutation.  What a caller may rely on: after ANY entry of this header that changes the values -- lsq_mat_set_values / _async,
- * lsq_mat_values + writes + lsq_mat_refresh, lsq_mat_set_colscale / lsq_mat_colscale_changed, lsq_fd_jacobian, the g! of
- * lsq_model_g -- every reader (lsq_mat_get_values, lsq_mul, lsq_colsumabs2, lsq_rowsumabs2, lsq_ldiv*, lsq_sparse_gram, the
+ * lsq_mat_values + writes + lsq_mat_refresh, lsq_mat_set_colscale / lsq_mat_colscale_changed, lsq_mat_scale_rows,
+ * lsq_fd_jacobian, the g! of lsq_model_g and of lsq_loss_g -- every reader (lsq_mat_get_values, lsq_mul, lsq_colsumabs2, lsq_rowsumabs2, lsq_ldiv*, lsq_sparse_gram, the
  * covariance entries, the loops) sees those values and nothing older, in whatever order mutations and readers are mixed, and
  * gives the bits it gives on a freshly created handle holding the same V and s.
  * lsq_mat_values returns the values as they are at that moment; the pointer is for writing until the next entry that changes
@@ -166,6 +166,15 @@ double *lsq_mat_values(lsq_mat *J);
  * lsq_mat_refresh first brings the CSC-ordered copy up to date with such a g!, then takes it as the authority: called with
  * nothing written it changes no value (so does lsq_mat_set_colscale(J, NULL) on a handle that has no scale). */
 int lsq_mat_refresh(lsq_mat *J);
+/* J <- diag(w) J: stored entry (i, j) becomes fl(v * w_i), one product; d_w: m device doubles, read during the call's launches.
+ * A mutation under the freshness contract: the CSC-ordered copy is made current first (a g! of lsq_model_g may have written
+ * the mirrors only), scaled in place -- one read and one write per stored value; a plain CSC handle also reads its row
+ * indices, block-diagonal and bordered handles get the row from the position -- and then taken as the authority exactly as by
+ * lsq_mat_refresh, so every mirror, sliced layout and windowed copy holds the scaled values.  Behind lsq_mat_set_values_async
+ * the scaling waits for the copy on the device.  Stream-ordered, no atomics, no host wait; 0, negative, NaN factors are taken
+ * as they are.  LSQ_EARG, with the reason in lsq_last_error: an operator handle (no stored values), a handle with a column scale
+ * set (its stored values are V: they would keep every factor while a g! only changes s), a null argument. */
+int lsq_mat_scale_rows(lsq_mat *J, const double *d_w);
 /* Which layouts the handle has built and which mode it is in (host code: launches nothing, waits for nothing, changes nothing):
  * h_out[0] kind (0 dense, 1 CSC -- block-diagonal and bordered handles included --, 2 operator); [1] sliced rows built (J*x),
  * [2] their column windows, [3] output rows per block; [4] sliced columns built (J'y), [5] their gather windows, [6] column
@@ -636,6 +645,60 @@ typedef struct {
 int lsq_optimize_batched(lsq_ctx *ctx, int optimizer, int solver_kind, lsq_mat *J, double *d_x,
                          double *d_fcur, lsq_f_callback f, lsq_g_callback g, void *user,
                          const lsq_options *opt, void *batched_result);
+
+/* ---- robust losses and observation weights: a wrapper around the problem ----
+ * Measured data come with per-point uncertainties sigma_i and with outliers.  With z_i = f_i / sigma_i (z_i = f_i without
+ * sigmas), a_i = |z_i| / c (c > 0: the loss scale) and a loss rho(s), s = a^2, the WRAPPED problem has
+ *   the residual  r~_i = sign(z_i) c sqrt(rho(a_i^2))
+ *   the Jacobian  J~ = diag(w_i / sigma_i) J,   w_i = d r~_i / d z_i = rho'(s) sqrt(s) / sqrt(rho(s)),  w_i = 1 at s = 0.
+ * It is an exact least-squares problem: sum(abs2, r~) = c^2 sum(rho), twice the robust cost, and J~'r~ = J'(rho' f / sigma^2),
+ * the exact gradient of that cost.  So the reference's accept ratio, convergence flags and ssr, every solver, lsq_optimize,
+ * lsq_optimize_batched, g = NULL (central differences of the wrapped f ARE the Jacobian of r~) and every covariance entry
+ * apply unchanged: at the solution a covariance entry sees J~ in the handle and r~ in d_fcur -- with LSQ_LOSS_LINEAR and sigmas
+ * the textbook weighted covariance.  (Not the Triggs / scipy scaling, whose Jacobian carries a second-order correction and
+ * whose residual scale is sqrt(rho'): that one is not the gradient of an exact sum of squares.)
+ *   kind              r~                                                       w
+ *   LSQ_LOSS_LINEAR   z                                                        1
+ *   LSQ_LOSS_HUBER    a <= 1: z;  a > 1: q = sqrt(2a - 1) (2 sqrt(a / 2) when   1;  1 / q
+ *                     a > 2^1022: 2a would overflow), copysign(c q, z)
+ *   LSQ_LOSS_SOFT_L1  t = sqrt(1 + a a) (t = a when a > 2^500),                1 / (t q)
+ *                     q = sqrt(2 / (t + 1)), z q
+ *   LSQ_LOSS_CAUCHY   a < 2^-27: z.  Else L = log1p(a a) (2 log(a) when        1;  1 / ((1 + a a) q)
+ *                     a > 2^500), q = sqrt(L) / a, z q                             ((1 / (a q)) / a when a > 2^500:
+ *                                                                                  1 / a^2 would underflow)
+ * Every operation of the table is one IEEE operation in that order; the row factor applied to J is w_i / sigma_i, one division.
+ * Linear, Huber and soft-l1 give the bits of a host evaluation in that order (leastsquaresoptim.jl_amd/api.py: loss_transform);
+ * Cauchy contains a log1p and agrees to rounding.  Signed zeros pass through; a NaN or an infinite f_i comes out as it went in
+ * (w_i = 1 for NaN, 0 for +-Inf, except LSQ_LOSS_LINEAR: 1), so check_isfinite reports the index it would without a loss;
+ * 0 <= w <= 1 and |r~| <= |z|.
+ * lsq_loss_create: d_sigma_or_null is NULL or m device doubles, COPIED (the caller may free them); the object owns three
+ * m-vectors (that copy, a raw residual, the row factors).  LSQ_EARG: an unknown kind, a scale that is not finite and positive,
+ * a sigma that is not finite and positive (one readback at creation; the message names the index).  m < 1: LSQ_EDIM.
+ * The handle is spelled void * for the reason lsq_optimize_batched spells its result so.
+ * lsq_loss_eval: the transform itself, one elementwise kernel: d_f (m raw residuals) -> d_rt_or_null (r~; may be d_f itself) and
+ * d_rowfactor_or_null (w / sigma), both in one pass.  h_stats_or_null: NULL (stream-ordered, nothing waits) or two host doubles:
+ * [0] = sum(abs2, r~) through lsq_sumsq (the bits the loops compute), [1] = the number of rows with a > 1.
+ * lsq_loss_set_problem gives the object the caller's own f! and g! (g_or_null = NULL: none) and their user pointer; then
+ * lsq_optimize / lsq_optimize_batched / lsq_fd_jacobian are handed lsq_loss_f(), lsq_loss_g() -- or a null g for central
+ * differences -- and the loss handle as `user`:
+ *   lsq_loss_f  calls the inner f into d_out and transforms it in place;
+ *   lsq_loss_g  calls the inner g, evaluates the inner f at the same d_x into the object's scratch (one evaluation the loop does
+ *               not count, like the reference's finite-difference closure; nothing is cached from an earlier f call:
+ *               lsq_optimize_batched hands g per-block points no f call has seen), derives the row factors and calls
+ *               lsq_mat_scale_rows.
+ * A failure inside either returns non-zero, so the loop reports LSQ_ECALLBACK, and lsq_last_error keeps the wrapper's reason
+ * (the reason outlives the loop's generic "user callback reported failure" only; the next loop, solve or handle mutation
+ * starts clean):
+ * an inner callback failed, lsq_loss_set_problem was never called, J has another row count than m, or the handle is one
+ * lsq_mat_scale_rows refuses.  The handle and the loss object stay usable afterwards.
+ * Sharded and row-sharded runs (allreduce / row_allreduce in the options) with a loss are not covered. */
+enum { LSQ_LOSS_LINEAR = 0, LSQ_LOSS_HUBER = 1, LSQ_LOSS_SOFT_L1 = 2, LSQ_LOSS_CAUCHY = 3 };
+int lsq_loss_create(lsq_ctx *ctx, int kind, double scale, int m, const double *d_sigma_or_null, void **out);
+int lsq_loss_destroy(void *loss);
+int lsq_loss_set_problem(void *loss, lsq_f_callback f, lsq_g_callback g_or_null, void *user);
+lsq_f_callback lsq_loss_f(void);      /* pass these with user = the loss handle */
+lsq_g_callback lsq_loss_g(void);
+int lsq_loss_eval(void *loss, const double *d_f, double *d_rt_or_null, double *d_rowfactor_or_null, double *h_stats_or_null);
 
 /* ---- built-in device-side model for the synthetic benchmarks:
  *      r(x) = A tanh(x) - b,  J = A diag(1 - tanh(x)^2); A has J's pattern. ---- */

@@ -30,6 +30,7 @@ PRECOND_LDIV_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
 OK, EDIM, ENOTPD, ERANK, ENONFINITE, EBOUNDS, EHIP, EARG, ECALLBACK, ERCCL = range(10)
 QR, CHOLESKY, LSMR, BLOCK_QR, SCHUR, BORDERED_QR = 0, 1, 2, 3, 4, 5
 DOGLEG, LEVENBERG_MARQUARDT = 0, 1
+LOSS_KINDS = {"linear": 0, "huber": 1, "soft_l1": 2, "cauchy": 3}
 
 
 class Options(C.Structure):
@@ -127,6 +128,7 @@ def lib():
         "lsq_emul": (i, [vp, i, vp, vp, vp]),
         "lsq_mat_values": (vp, [vp]),
         "lsq_mat_refresh": (i, [vp]),
+        "lsq_mat_scale_rows": (i, [vp, vp]),
         "lsq_mat_layout": (i, [vp, c_ip]),
         "lsq_mat_set_colscale": (i, [vp, vp]),
         "lsq_mat_colscale_changed": (i, [vp]),
@@ -181,6 +183,12 @@ def lib():
         "lsq_optimize_batched": (i, [vp, i, i, vp, vp, vp, F_CALLBACK, G_CALLBACK, vp, C.POINTER(Options),
                                      C.POINTER(BatchedResult)]),
         "lsq_fd_jacobian": (i, [vp, vp, vp, F_CALLBACK, vp]),
+        "lsq_loss_create": (i, [vp, i, d, i, vp, pvp]),
+        "lsq_loss_destroy": (i, [vp]),
+        "lsq_loss_set_problem": (i, [vp, F_CALLBACK, G_CALLBACK, vp]),
+        "lsq_loss_f": (F_CALLBACK, []),
+        "lsq_loss_g": (G_CALLBACK, []),
+        "lsq_loss_eval": (i, [vp, vp, vp, vp, c_dp]),
         "lsq_csc_greedy_colouring": (i, [i, i, c_ip, c_ip, c_ip, c_ip]),
         "lsq_mat_set_fd_colouring": (i, [vp, c_ip, c_ip]),
         "lsq_mat_fd_colouring": (i, [vp, c_ip, c_ip]),

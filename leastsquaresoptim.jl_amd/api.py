@@ -606,6 +606,15 @@ class DeviceMatrix:
         """lsq_mat_refresh: after a device-side write through lsq_mat_values."""
         check(lib().lsq_mat_refresh(self.h))
 
+    def scale_rows(self, w):
+        """lsq_mat_scale_rows: J <- diag(w) J, every stored entry times the factor of its row (one product), in every layout
+        of the handle.  `w`: a DeviceVector of m factors or m host values.  An operator or a column-scaled handle raises
+        ArgumentError."""
+        dw = w if hasattr(w, "ptr") else DeviceVector(self.ctx, self.m, w)
+        if dw.n != self.m:
+            raise DimensionMismatch(_lib.EDIM, "row factors have length %d, expected %d" % (dw.n, self.m))
+        check(lib().lsq_mat_scale_rows(self.h, dw.ptr))
+
     def layout(self):
         """lsq_mat_layout: which layouts the handle built and which mode it is in (host code, changes nothing)."""
         return mat_layout(self.h)
@@ -1154,6 +1163,181 @@ def sparse_gram(Jd, damp=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# robust losses and observation weights (include/lsqhip.h: lsq_loss_create)
+# ------------------------------------------------------------------------------------------------
+LOSSES = tuple(_lib.LOSS_KINDS)
+_DBL_MAX = float(np.finfo(np.float64).max)
+
+
+def _loss_arguments(loss, f_scale, sigma, m=None):
+    """What lsq_loss_create checks, on the host: (loss, scale, sigma as a float64 array or None)."""
+    if loss not in _lib.LOSS_KINDS:
+        raise ArgumentError(_lib.EARG, "unknown loss %r (one of %s)" % (loss, ", ".join(LOSSES)))
+    c = float(f_scale)
+    if not 0.0 < c <= _DBL_MAX:
+        raise ArgumentError(_lib.EARG, "the loss scale must be finite and positive (got %g)" % c)
+    if sigma is None:
+        return loss, c, None
+    sg = np.ascontiguousarray(sigma, dtype=np.float64).reshape(-1)
+    if m is not None and sg.size != m:
+        raise DimensionMismatch(_lib.EDIM, "sigma has length %d, expected %d" % (sg.size, m))
+    bad = np.flatnonzero(~((sg > 0.0) & (sg <= _DBL_MAX)))
+    if bad.size:
+        raise ArgumentError(_lib.EARG, "sigma must be finite and positive, entry %d is %g" % (bad[0], sg[bad[0]]))
+    return loss, c, sg
+
+
+def loss_transform(f, loss, f_scale=1.0, sigma=None):
+    """The numpy twin of lsq_loss_eval and the normative statement of the transform: raw residuals f -> (rt, rowfactor) with
+    z = f / sigma, a = |z| / c, rt = sign(z) c sqrt(rho(a^2)) and rowfactor = w / sigma, w = d rt / d z.  Every line is one
+    IEEE operation per element in the order of the table in include/lsqhip.h, so "linear", "huber" and "soft_l1" have the
+    device's bits ("cauchy" contains a log1p and agrees to rounding).  NaN and +-Inf pass through unchanged with w = 1 / 0
+    ("linear": 1), signed zeros too."""
+    f = np.asarray(f, dtype=np.float64)
+    loss, c, sg = _loss_arguments(loss, f_scale, sigma, f.size)
+    with np.errstate(all="ignore"):
+        z = f / sg if sg is not None else f.copy()
+        a = np.abs(z) / c
+        rt, w = z.copy(), np.ones_like(z)
+        if loss != "linear":
+            fin = a <= _DBL_MAX
+            w[~fin] = np.where(np.isnan(a[~fin]), 1.0, 0.0)
+            if loss == "huber":
+                sel = fin & (a > 1.0)
+                ah = a[sel]
+                q = np.where(ah > 2.0 ** 1022, 2.0 * np.sqrt(0.5 * ah), np.sqrt(2.0 * ah - 1.0))    # (2a would overflow)
+                rt[sel] = np.copysign(c * q, z[sel])
+                w[sel] = 1.0 / q
+            elif loss == "soft_l1":
+                sel = fin
+                aa = a[sel]
+                t = np.where(aa > 2.0 ** 500, aa, np.sqrt(1.0 + aa * aa))
+                q = np.sqrt(2.0 / (t + 1.0))
+                rt[sel] = z[sel] * q
+                w[sel] = 1.0 / (t * q)
+            else:
+                sel = fin & (a >= 2.0 ** -27)
+                aa = a[sel]
+                big = aa > 2.0 ** 500
+                L = np.where(big, 2.0 * np.log(aa), np.log1p(aa * aa))
+                q = np.sqrt(L) / aa
+                rt[sel] = z[sel] * q
+                w[sel] = np.where(big, (1.0 / (aa * q)) / aa, 1.0 / ((1.0 + aa * aa) * q))
+        rowfactor = w / sg if sg is not None else w
+    return rt, rowfactor
+
+
+def _scale_rows_host(J, rowfactor):
+    """J <- diag(rowfactor) J in place on a host Jacobian: one product per stored value (lsq_mat_scale_rows' arithmetic)."""
+    if _is_bordered(J) or _is_blockdiag(J):
+        B, mb, nb = J.nblocks, J.mb, J.nb
+        J.data[:B * mb * nb].reshape(B, nb, mb)[:] *= rowfactor.reshape(B, 1, mb)
+        if _is_bordered(J):
+            J.border[:, :] *= rowfactor[:, None]
+    elif _is_sparse(J):
+        J.data *= rowfactor[J.indices]
+    else:
+        J *= rowfactor[:, None]
+
+
+def robust_twin(f_, g_, loss, f_scale=1.0, sigma=None):
+    """(f_, g_) of the wrapped problem on the host, built on loss_transform: what lsq_loss_f / lsq_loss_g compute on the
+    device.  The wrapped g_ calls g_, evaluates f_ itself at the same x (nothing is cached from an earlier f_ call) and
+    scales the rows of J -- a dense array, a scipy.sparse CSC matrix in canonical order, a BlockDiagonal or a
+    BorderedBlockDiagonal.  g_ = None gives (f_, None): central differences of the wrapped f_ are the Jacobian of the wrapped
+    residual."""
+    loss, c, sg = _loss_arguments(loss, f_scale, sigma)
+
+    def rf_(out, x):
+        f_(out, x)
+        out[:] = loss_transform(out, loss, c, sg)[0]
+
+    if g_ is None:
+        return rf_, None
+
+    def rg_(J, x):
+        g_(J, x)
+        raw = np.zeros(J.shape[0])
+        f_(raw, x)
+        _scale_rows_host(J, loss_transform(raw, loss, c, sg)[1])
+
+    return rf_, rg_
+
+
+class Loss:
+    """The loss object of the C ABI (lsq_loss_create): kind, scale, m rows and a device copy of the sigmas.  `eval` is
+    lsq_loss_eval on DeviceVectors; F / G are lsq_loss_f() / lsq_loss_g(), to be handed to a loop with `h` as the user
+    pointer once set_problem has given it the inner callbacks."""
+
+    def __init__(self, ctx, loss="linear", f_scale=1.0, m=None, sigma=None):
+        if m is None:
+            if sigma is None:
+                raise ValueError("Loss needs m or sigma")
+            m = len(sigma)
+        self.ctx, self.loss, self.f_scale, self.m = ctx, loss, float(f_scale), int(m)
+        ds = DeviceVector(ctx, self.m, sigma) if sigma is not None and self.m >= 1 else None
+        h = C.c_void_p()
+        try:      # (an unknown name goes to the library as -1: its refusal, its message)
+            check(lib().lsq_loss_create(ctx.h, _lib.LOSS_KINDS.get(loss, -1), self.f_scale, self.m, _ptr(ds), C.byref(h)))
+        finally:
+            if ds is not None:
+                ds.free()
+        self.h = h
+        self.F, self.G = lib().lsq_loss_f(), lib().lsq_loss_g()
+        self._raw = DeviceVector(ctx, self.m)
+        self._inner = None
+
+    def set_problem(self, F, G=None):
+        """lsq_loss_set_problem: the inner f! / g! as ctypes callbacks (G = None: none)."""
+        self._inner = (F, G)        # (keeps the ctypes callbacks alive)
+        check(lib().lsq_loss_set_problem(self.h, F, G if G is not None else _lib.G_CALLBACK(), None))
+
+    def eval(self, f, rt=None, rowfactor=None, stats=False):
+        """lsq_loss_eval: f (m raw residuals) -> rt (may be f itself) and rowfactor, DeviceVectors or None.  stats=True
+        returns (sum(abs2, rt), rows with a > 1); otherwise nothing is read back."""
+        for v in (f, rt, rowfactor):
+            if v is not None and v.n != self.m:
+                raise DimensionMismatch(_lib.EDIM, "vector has length %d, expected %d" % (v.n, self.m))
+        st = (C.c_double * 2)() if stats else None
+        check(lib().lsq_loss_eval(self.h, f.ptr, _ptr(rt), _ptr(rowfactor), st))
+        return (float(st[0]), int(st[1])) if stats else None
+
+    def transform(self, f):
+        """eval on m host values: (rt, rowfactor, sum(abs2, rt), rows with a > 1)."""
+        self._raw.set(f)
+        drf = DeviceVector(self.ctx, self.m)
+        ssr, out = self.eval(self._raw, self._raw, drf, stats=True)
+        return self._raw.get(), drf.get(), ssr, out
+
+    def free(self):
+        if getattr(self, "h", None):
+            lib().lsq_loss_destroy(self.h)
+            self.h = None
+            self._raw.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _new_loss(ctx, loss, f_scale, sigma, m):
+    """The loss object of a loop call, or None for the defaults (the call is then exactly the one without these arguments)."""
+    if loss == "linear" and sigma is None:
+        return None
+    loss, c, sg = _loss_arguments(loss, f_scale, sigma, m)
+    return Loss(ctx, loss, c, m, sg)
+
+
+def _loss_outliers(lossobj, host, dx):
+    """h_stats[1] at the solution: one more evaluation of the raw f_ there."""
+    if host._fcb(lossobj._raw.ptr, dx.ptr, None) != 0:
+        raise host.err[-1]
+    return lossobj.eval(lossobj._raw, stats=True)[1]
+
+
+# ------------------------------------------------------------------------------------------------
 # problem / result types
 # ------------------------------------------------------------------------------------------------
 class OptimizationState:
@@ -1557,6 +1741,17 @@ class _HostCallbacks:
         if self.device_fd:
             self.nls.J.data[:] = self.Jd.values()
 
+    def fetch_scaled_jacobian(self):
+        """With a loss the handle holds diag(w / sigma) J, the staging buffer the raw values of the last g!: nls.J gets the
+        handle's (after release(), which has handed J.data back)."""
+        if self.is_op:
+            return
+        v = self.Jd.values()
+        if self.Jd.sparse:
+            self.nls.J.data[:] = v
+        else:
+            self.nls.J[:, :] = v.reshape((self.m, self.n), order="F")
+
     def release(self):
         stage = self.stage
         if stage is None:
@@ -1643,9 +1838,14 @@ def _run_native(ctx, optimizer_kind, solver_kind, Jd, dx, dy, fcb, gcb, user, x_
 
 def optimize_(nls, optimizer=None, x_tol=1e-8, f_tol=1e-8, g_tol=1e-8, iterations=1000, delta=None,
               store_trace=False, show_trace=False, show_every=1, lower=(), upper=(), ctx=None,
-              full_trace=False, row_allreduce=None, global_rows=0):
+              full_trace=False, row_allreduce=None, global_rows=0, loss="linear", f_scale=1.0, sigma=None):
     """optimize!(nls, optimizer; kwargs...)  -- types.jl:207-209 then
     levenberg_marquardt.jl:39-144 / dogleg.jl:41-203.  Mutates nls.x, nls.y, nls.J in place.
+    loss ("linear", "huber", "soft_l1", "cauchy"), f_scale and sigma (m per-point uncertainties): the loop minimises the robust,
+    weighted cost through the wrapped problem of include/lsqhip.h (lsq_loss_create) -- f_ / g_ stay the raw residual and its
+    Jacobian; afterwards nls.y holds the wrapped residual, nls.J the wrapped Jacobian, r.ssr = f_scale^2 sum(rho), and the
+    result carries loss, f_scale and outliers (rows with |f / sigma| > f_scale at the solution).  With the defaults nothing of
+    this exists.  An allocated problem takes them at allocation.
     On a BorderedBlockDiagonal Jacobian Cholesky() without an optimizer means LevenbergMarquardt(Cholesky()), and
     Dogleg(Cholesky()) raises ArgumentError (it does not exist there); LevenbergMarquardt / Dogleg with LSMR() run as on any
     sparse Jacobian."""
@@ -1655,12 +1855,16 @@ def optimize_(nls, optimizer=None, x_tol=1e-8, f_tol=1e-8, g_tol=1e-8, iteration
         # allocation (types.jl:141-160); nothing is allocated here, on the host or on the device
         if optimizer is not None:
             raise TypeError("an allocated problem carries its optimizer (types.jl:152-157)")
+        if loss != "linear" or sigma is not None or f_scale != 1.0:
+            raise TypeError("an allocated problem carries its loss: give loss, f_scale and sigma to LeastSquaresProblemAllocated")
         ctx, optimizer, solver = allocated.ctx, allocated.optimizer, allocated.solver
     else:
         solver = default_solver(optimizer.solver if optimizer is not None else None, nls.J)   # (refusals need no device)
         optimizer = default_optimizer(optimizer, solver, nls.J)
         ctx = ctx or default_context()
     n, m = len(nls.x), len(nls.y)
+    if allocated is None and (loss != "linear" or sigma is not None):
+        loss, f_scale, sigma = _loss_arguments(loss, f_scale, sigma, m)      # (refusals before anything is allocated)
     is_op = isinstance(nls.J, DeviceOperator)
     if allocated is not None:
         Jd, dx, dy = allocated._Jd, allocated._dx, allocated._dy
@@ -1671,7 +1875,12 @@ def optimize_(nls, optimizer=None, x_tol=1e-8, f_tol=1e-8, g_tol=1e-8, iteration
         dx, dy = DeviceVector(ctx, n, nls.x), DeviceVector(ctx, m, nls.y)
     host = _HostCallbacks(ctx, nls, Jd, allocated._stage if allocated is not None else None)
     err = host.err
-    F, G = host.F, host.G
+    F, G, user = host.F, host.G, None
+    lossobj = allocated._loss if allocated is not None else _new_loss(ctx, loss, f_scale, sigma, m)
+    if lossobj is not None:     # the host callbacks become the inner problem; the loop gets the wrapper (a null g! stays null)
+        lossobj.set_problem(host.F, None if host.device_fd else host.G)
+        F, user = lossobj.F, lossobj.h
+        G = host.G if host.device_fd else lossobj.G
     tracing = store_trace or show_trace or full_trace
     st = res = tr = None
     try:
@@ -1683,7 +1892,7 @@ def optimize_(nls, optimizer=None, x_tol=1e-8, f_tol=1e-8, g_tol=1e-8, iteration
             pc = _precond_trampoline(solver.preconditioner, ctx, Jd)
         # row_allreduce: a rowshard.RcclRowAllreduce / HostStagedRowAllreduce -- nls then holds this rank's ROWS of one
         # larger problem (J, y local; x replicated), SURVEY 8f-4
-        st, res, tr = _run_native(ctx, optimizer.kind, solver.kind, Jd, dx, dy, F, G, None, x_tol, f_tol,
+        st, res, tr = _run_native(ctx, optimizer.kind, solver.kind, Jd, dx, dy, F, G, user, x_tol, f_tol,
                                   g_tol, iterations, delta, lower, upper, tracing, n, preconditioner=pc,
                                   general_preconditioner=gpc,
                                   row_allreduce=row_allreduce.callback if row_allreduce is not None else None,
@@ -1693,18 +1902,27 @@ def optimize_(nls, optimizer=None, x_tol=1e-8, f_tol=1e-8, g_tol=1e-8, iteration
         host.release()
         if st is not None:
             host.fetch_jacobian()
+            if lossobj is not None:
+                host.fetch_scaled_jacobian()
             # optimize! mutates nls.x / nls.y in place (levenberg_marquardt.jl:46): when an iteration throws
             # (RankDeficientException, IsFiniteException, ...) they hold that iteration's iterate, as in the reference
             nls.x[:] = dx.get()
             nls.y[:] = dy.get()
-    if err:
-        raise err[0]
-    if st == _lib.ENONFINITE:
-        e = _lib.IsFiniteException(st, lib().lsq_last_error().decode())
-        e.indices = [res.bad_index]
-        raise e
-    check(st)
+    try:
+        if err:
+            raise err[0]
+        if st == _lib.ENONFINITE:
+            e = _lib.IsFiniteException(st, lib().lsq_last_error().decode())
+            e.indices = [res.bad_index]
+            raise e
+        check(st)
+        outliers = _loss_outliers(lossobj, host, dx) if lossobj is not None else None
+    finally:
+        if lossobj is not None and allocated is None:
+            lossobj.free()
     r = LeastSquaresResult()
+    if lossobj is not None:
+        r.loss, r.f_scale, r.outliers = lossobj.loss, lossobj.f_scale, outliers
     r.optimizer = optimizer.name
     r.minimizer = nls.x
     r.ssr = float(res.ssr)
@@ -1868,34 +2086,51 @@ def _run_native_batched(ctx, optimizer_kind, solver_kind, Jh, shape, dx, dy, fcb
 
 
 def optimize_batched_(nls, optimizer=None, x_tol=1e-8, f_tol=1e-8, g_tol=1e-8, iterations=1000, delta=None,
-                      lower=(), upper=(), ctx=None, full_trace=False):
+                      lower=(), upper=(), ctx=None, full_trace=False, loss="linear", f_scale=1.0, sigma=None):
     """B runs of optimize! in one device loop: nls.J is a BlockDiagonal(B, mb, nb) and fit b is the problem made of residual
     rows b*mb .. and parameters b*nb .. -- its own trust region, accept decisions, convergence test and counts
     (levenberg_marquardt.jl:39-144 / dogleg.jl:41-203 per block; include/lsqhip.h: lsq_optimize_batched).  f_ / g_ have the
     signatures optimize_ uses and see the stacked x, y, J.data; they must be block-separable and deterministic.  Default
     optimizer: LevenbergMarquardt(Cholesky()).  A fit that fails (status[b] != 0) does not end the call.  Mutates nls.x,
-    nls.y, nls.J; returns a BatchedResult."""
+    nls.y, nls.J; returns a BatchedResult.  loss, f_scale, sigma: as for optimize_ (sigma has m entries; the result's
+    `outliers` counts all blocks)."""
     n, m = len(nls.x), len(nls.y)
     optimizer, solver = _batched_arguments(nls.J, optimizer, n, lower, upper)
+    if loss != "linear" or sigma is not None:
+        loss, f_scale, sigma = _loss_arguments(loss, f_scale, sigma, m)      # (refusals before anything is allocated)
     ctx = ctx or default_context()
     J = nls.J
     Jd = DeviceMatrix(ctx, J)
     dx, dy = DeviceVector(ctx, n, nls.x), DeviceVector(ctx, m, nls.y)
     host = _HostCallbacks(ctx, nls, Jd)
+    F, G, user = host.F, host.G, None
+    lossobj = _new_loss(ctx, loss, f_scale, sigma, m)
+    if lossobj is not None:
+        lossobj.set_problem(host.F, None if host.device_fd else host.G)
+        F, user = lossobj.F, lossobj.h
+        G = host.G if host.device_fd else lossobj.G
     st = r = None
     try:
         host.bind()
-        st, r = _run_native_batched(ctx, optimizer.kind, solver.kind, Jd.h, (J.nblocks, J.mb, J.nb), dx, dy, host.F, host.G,
-                                    None, x_tol, f_tol, g_tol, iterations, delta, lower, upper, full_trace, optimizer.name)
+        st, r = _run_native_batched(ctx, optimizer.kind, solver.kind, Jd.h, (J.nblocks, J.mb, J.nb), dx, dy, F, G,
+                                    user, x_tol, f_tol, g_tol, iterations, delta, lower, upper, full_trace, optimizer.name)
     finally:
         host.release()
         if st is not None:
             host.fetch_jacobian()
+            if lossobj is not None:
+                host.fetch_scaled_jacobian()
             nls.x[:] = dx.get()
             nls.y[:] = dy.get()
-    if host.err:
-        raise host.err[0]
-    check(st)
+    try:
+        if host.err:
+            raise host.err[0]
+        check(st)
+        if lossobj is not None:
+            r.loss, r.f_scale, r.outliers = lossobj.loss, lossobj.f_scale, _loss_outliers(lossobj, host, dx)
+    finally:
+        if lossobj is not None:
+            lossobj.free()
     r.minimizer = nls.x
     r.jacobian = nls.J
     Jd.free()
@@ -1906,9 +2141,10 @@ class LeastSquaresProblemAllocated:
     """LeastSquaresProblemAllocated(nls, optimizer) (types.jl:141-160, exported by the reference): the problem
     together with its optimizer, its solver and every buffer they need, allocated once; `optimize_(nlsa)` can then
     be called repeatedly (e.g. from different starting points written into `nlsa.x`) without allocating -- the
-    device Jacobian handle, the vectors and, inside the library, the loop/solver workspace are all reused."""
+    device Jacobian handle, the vectors and, inside the library, the loop/solver workspace are all reused.
+    loss, f_scale, sigma: the robust loss and the observation weights of optimize_, taken here."""
 
-    def __init__(self, nls, optimizer=None, ctx=None):
+    def __init__(self, nls, optimizer=None, ctx=None, loss="linear", f_scale=1.0, sigma=None):
         if not isinstance(nls, LeastSquaresProblem):
             raise TypeError("LeastSquaresProblemAllocated(nls::LeastSquaresProblem, optimizer)")
         self.ctx = ctx or default_context()
@@ -1922,8 +2158,13 @@ class LeastSquaresProblemAllocated:
         self._dy = DeviceVector(self.ctx, len(nls.y), nls.y)
         # the page-locked staging buffer of the Jacobian uploads is part of the allocated problem too
         self._stage = None if isinstance(self._Jd, DeviceOperator) else PinnedBuffer(self.ctx, self._Jd.nnz)
+        # ... and so is the loss object (loss, f_scale, sigma are taken here: optimize_ allocates nothing)
+        self._loss = _new_loss(self.ctx, loss, f_scale, sigma, len(nls.y))
 
     def free(self):
+        if getattr(self, "_loss", None) is not None:
+            self._loss.free()
+            self._loss = None
         if self._Jd is not None and not isinstance(self._Jd, DeviceOperator):
             self._Jd.free()
         self._Jd = None
@@ -1935,7 +2176,7 @@ class LeastSquaresProblemAllocated:
 def optimize(f, x, optimizer, autodiff="central", J=None, colouring=None, **kwargs):
     """optimize(f, x, optimizer; kwargs...) -- types.jl:182-184 (x is copied; f returns a vector).
     autodiff="central_coloured" with J = a scipy.sparse pattern (and optionally a colouring): coloured central differences on
-    the device, as LeastSquaresProblem describes."""
+    the device, as LeastSquaresProblem describes.  loss=, f_scale= and sigma= go to optimize_ with the other keywords."""
     x0 = np.array(x, dtype=np.float64)
     out0 = np.atleast_1d(np.asarray(f(x0), dtype=np.float64))
 

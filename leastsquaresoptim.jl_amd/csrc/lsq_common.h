@@ -12,6 +12,7 @@
 #include "../../include/lsqhip.h"
 
 void lsq_set_error(const char *fmt, ...);
+void lsq_keep_error_as_callback_reason();   // the message set last survives the caller's "user callback reported failure"
 
 #define LSQ_HIP(call)                                                                      \
     do {                                                                                   \

@@ -762,6 +762,104 @@ extern "C" int lsq_mat_refresh(lsq_mat *J) {
     return mat_values_written(J);
 }
 
+// ---- row scaling J <- diag(w) J (include/lsqhip.h: lsq_mat_scale_rows) --------------------------------------------
+// One read and one write per stored value, fl(v * w_i) each; no atomics, nothing waits.
+// Dense column-major (also the border of a bordered handle: m x ng): workgroup x owns LSQ_NT rows, a lane keeps its row's
+// factor in a register and walks the columns y, y + gridDim.y, ..; a wavefront's accesses are 64 consecutive doubles.
+__global__ void __launch_bounds__(LSQ_NT)
+k_scale_rows_dense(int m, int n, const double *__restrict__ w, double *__restrict__ v) {
+    const int i = blockIdx.x * LSQ_NT + threadIdx.x;
+    if (i >= m) return;
+    const double wi = w[i];
+    double *p = v + i;
+    const long long gy = gridDim.y;
+    const size_t step = (size_t)gy * m;
+    long long j = blockIdx.y;
+    for (; j + 3 * gy < n; j += 4 * gy) {   // four independent loads in flight
+        double *q0 = p + (size_t)j * m, *q1 = q0 + step, *q2 = q1 + step, *q3 = q2 + step;
+        const double a0 = *q0, a1 = *q1, a2 = *q2, a3 = *q3;
+        *q0 = a0 * wi; *q1 = a1 * wi; *q2 = a2 * wi; *q3 = a3 * wi;
+    }
+    for (; j < n; j += gy) p[(size_t)j * m] *= wi;
+}
+
+// plain CSC: the loads of val and rowval are coalesced over k, the gather of w is the only irregular access
+__global__ void __launch_bounds__(LSQ_NT)
+k_scale_rows_csc(long long nnz, const int *__restrict__ rowval, const double *__restrict__ w, double *__restrict__ val) {
+    for (long long k = blockIdx.x * (long long)LSQ_NT + threadIdx.x; k < nnz; k += (long long)gridDim.x * LSQ_NT)
+        val[k] *= w[rowval[k]];
+}
+
+// The blocks of a block-diagonal or bordered handle, nzval order [block][column][row]: entry k sits in row
+// (k / (mb nb)) mb + k mod mb.  A thread divides once, for its first entry; from then on both remainders advance by the
+// grid stride's own remainders (sp = stride mod mb nb, sr = stride mod mb, sb = (stride / (mb nb)) mb) with one conditional
+// subtraction each.  rowval is not read.
+__global__ void __launch_bounds__(LSQ_NT)
+k_scale_rows_blocks(int nloc, int mb, int P, int sp, int sr, int sb, const double *__restrict__ w, double *__restrict__ val) {
+    const int stride = gridDim.x * LSQ_NT;
+    int k = blockIdx.x * LSQ_NT + threadIdx.x;
+    if (k >= nloc) return;
+    int p = k % P, r = k % mb, base = (k / P) * mb;
+    for (;;) {
+        val[k] *= w[base + r];
+        if (nloc - k <= stride) return;      // (k + stride is never formed past nloc: no 32-bit overflow)
+        k += stride;
+        p += sp; base += sb;
+        if (p >= P) { p -= P; base += mb; }
+        r += sr;
+        if (r >= mb) r -= mb;
+    }
+}
+
+static int scale_rows_dense_launch(lsq_ctx *c, int m, int n, const double *w, double *v) {
+    if (m < 1 || n < 1) return LSQ_OK;
+    const int gx = lsq_div_up(m, LSQ_NT);
+    const int gy = std::max(1, std::min(n, std::min(65535, (c->num_cus * 16 + gx - 1) / gx)));
+    LSQ_LAUNCH(k_scale_rows_dense, dim3(gx, gy), dim3(LSQ_NT), 0, c->stream, m, n, w, v);
+    LSQ_HIP(hipGetLastError());
+    return LSQ_OK;
+}
+
+extern "C" int lsq_mat_scale_rows(lsq_mat *J, const double *d_w) {
+    LSQ_RANGE("lsq_mat_scale_rows");
+    if (!J || !d_w) {
+        lsq_set_error("lsq_mat_scale_rows: null argument");
+        return LSQ_EARG;
+    }
+    if (J->kind == LSQ_MAT_OP) {
+        lsq_set_error("lsq_mat_scale_rows: a matrix-free operator has no stored values to scale");
+        return LSQ_EARG;
+    }
+    if (J->d_cs_user) {
+        lsq_set_error("lsq_mat_scale_rows: the handle has a column scale (lsq_mat_set_colscale): its stored values are V, which "
+                      "would keep every row factor while a g! only changes s (remove the scale first)");
+        return LSQ_EARG;
+    }
+    lsq_ctx *c = J->ctx;
+    LSQ_TRY(lsq_ensure_csc(J));
+    if (J->kind == LSQ_MAT_DENSE) {
+        LSQ_TRY(scale_rows_dense_launch(c, J->m, J->n, d_w, J->d_dense));
+    } else if (J->nnz > 0) {
+        const int B = J->bd_blocks > 0 ? J->bd_blocks : J->br_blocks;
+        if (B > 0) {
+            const int mb = J->bd_blocks > 0 ? J->bd_mb : J->br_mb, nb = J->bd_blocks > 0 ? J->bd_nb : J->br_nb;
+            const int P = mb * nb, nloc = B * P;       // (nnz fits 32 bits on every CSC handle)
+            const int grid = std::min(lsq_div_up(nloc, LSQ_NT), c->num_cus * 16);
+            const int stride = grid * LSQ_NT;
+            LSQ_LAUNCH(k_scale_rows_blocks, dim3(grid), dim3(LSQ_NT), 0, c->stream, nloc, mb, P, stride % P, stride % mb,
+                       (stride / P) * mb, d_w, J->csc.d_val);
+            LSQ_HIP(hipGetLastError());
+            if (J->br_blocks > 0) LSQ_TRY(scale_rows_dense_launch(c, J->m, J->br_ng, d_w, J->csc.d_val + nloc));
+        } else {
+            const int grid = (int)std::min<long long>((J->nnz + LSQ_NT - 1) / LSQ_NT, (long long)c->num_cus * 16);
+            LSQ_LAUNCH(k_scale_rows_csc, dim3(grid), dim3(LSQ_NT), 0, c->stream, J->nnz, (const int *)J->csc.d_idx, d_w,
+                       J->csc.d_val);
+            LSQ_HIP(hipGetLastError());
+        }
+    }
+    return mat_values_written(J);    // what lsq_mat_refresh does from here on: every mirror and sliced layout follows
+}
+
 extern "C" int lsq_mat_layout(const lsq_mat *J, int h_out[12]) {
     if (!J || !h_out) {
         lsq_set_error("lsq_mat_layout: null argument");

@@ -12,6 +12,12 @@
 #include "lsq_common.h"
 
 static thread_local char g_err[512] = "";
+// A callback that belongs to the library (lsq_loss_f / lsq_loss_g) leaves its reason and returns non-zero; the loop that called
+// it then reports "user callback reported failure" like for any callback, and that one generic text does not replace the
+// reason.  The mark does not outlive the next entry of the C ABI that opens a range (every loop, lsq_fd_jacobian, the solves,
+// the handle mutations): a wrapper that failed when called directly cannot hide a later failure of somebody else's callback.
+static thread_local bool g_err_is_callback_reason = false;
+void lsq_keep_error_as_callback_reason() { g_err_is_callback_reason = true; }
 
 // ---- roctx ranges (lsq_common.h: LSQ_RANGE) ----------------------------------------------------
 static int (*g_roctx_push)(const char *) = nullptr;
@@ -32,10 +38,18 @@ static bool roctx_bind() {
     }();
     return bound;
 }
-LsqRange::LsqRange(const char *name) : on(roctx_bind()) { if (on) g_roctx_push(name); }
+LsqRange::LsqRange(const char *name) : on(roctx_bind()) {
+    g_err_is_callback_reason = false;
+    if (on) g_roctx_push(name);
+}
 LsqRange::~LsqRange() { if (on) g_roctx_pop(); }
 
 void lsq_set_error(const char *fmt, ...) {
+    if (g_err_is_callback_reason) {
+        // (the generic text may come twice: central differences report the wrapped f!, then the loop reports its g! thunk)
+        if (!strcmp(fmt, "user callback reported failure")) return;
+        g_err_is_callback_reason = false;
+    }
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
