@@ -459,6 +459,57 @@ int lsq_sparse_gram(lsq_mat *J, const double *d_damp, double *d_G);
  * solver that is not LSMR() or was created for another shape, a solver with a row all-reduce hook, d_cov and d_stderr both
  * NULL, d_f with m <= n, n > 16384.  n = 0: LSQ_OK, nothing is launched. */
 int lsq_sparse_covariance(lsq_solver *s, lsq_mat *J, const double *d_f, double *d_cov, double *d_stderr, int *h_info);
+/* Leverages and prediction variances of a dense fit from the QR() factor: the quadratic form q(a) = a' inv(J'J) a = ||X' P' a||^2
+ * with J P = Q R, X = inv(R), for the rows of J itself (q_i = h_i, the diagonal of the hat matrix J inv(J'J) J') or for new
+ * rows, and what follows from it and the residual.  J'J is never formed, and neither the n x n covariance nor J leaves the
+ * device.  `s` is an LSQ_QR solver created on the dense handle J (lsq_dense_create), either for_lm.  The factor, the rank
+ * decision, the retries and the allocation rules are those of lsq_dense_qr_covariance (above): whatever lsq_ldiv enqueues for
+ * this operand, run on a solver-owned zero right-hand side.  No damping is involved; J, d_A and d_f are not written; a solve
+ * after this call has the bits of a solve without it.
+ *   d_A = NULL: the rows of J; p and lda are ignored, there are m outputs and q_i = h_i.  A column-scaled handle means J S, as
+ *   everywhere else.
+ *   d_A non-NULL: p >= 1 rows in the parameter space the handle means (for a column-scaled handle: of J S), column-major as
+ *   p x n with leading dimension lda >= p (device); there are p outputs.  d_student and d_cook must then be NULL.
+ *   d_f: NULL, or the residual (m doubles, device).  d_se, d_student, d_cook and h_s2 need it.
+ *   d_q: NULL or the quadratic forms.  d_se, d_student, d_cook: NULL or, with s2 = lsq_sumsq(f) / (m - n) (also written to
+ *   *h_s2, a host double, when that is given), each line one IEEE operation in exactly this order:
+ *       sd     = sqrt(s2)
+ *       se_i   = sd * sqrt(q_i)                         the standard error of the prediction a_i'x: the band is y^ +- t * se
+ *       d_i    = 1 - h_i
+ *       t_i    = f_i / (sd * sqrt(d_i))                 the internally studentized residual
+ *       cook_i = ((t_i * t_i) * h_i) / (n * d_i)        Cook's distance, n converted to double
+ *   Nothing is clamped: an h_i that rounds to 1 or above (a row that alone determines a parameter) gives what IEEE arithmetic
+ *   gives for these lines -- a division by zero, the square root of a negative number: +-inf or NaN in t_i and cook_i.
+ *   h_info: NULL or one int, the rank the solve decided.
+ * The hot path is one kernel on the fp64 matrix unit (k_lev_tall, lsq_leverage.hip): one workgroup per 64 rows, Z = A P X
+ * accumulated tile by tile with k in index order and squared into the row sums at once; Z is never stored.  Row i's bits
+ * depend on row i and on X only: not on p, on where the row stands, on the other rows, on the run, or on
+ * lsq_debug_set(serial = 1); d_A = the values of J gives the bits of d_A = NULL.  No floating-point atomics.  When d_q is NULL
+ * and a derived output is asked for, the solver keeps the q's in a buffer of its own (grown on demand, freed with it).
+ * rank < n: LSQ_ERANK with lsq_dense_qr_covariance's message (rank and n); the outputs are unspecified and the solver stays
+ * usable for solves, covariances and further leverages.  A pseudo-inverse is not offered.
+ * LSQ_EARG, each with a message in lsq_last_error: a solver of another kind; a handle that is not dense; a shape other than the
+ * solver's; m < n; every output NULL; d_f with m <= n; d_se, d_student, d_cook or h_s2 without d_f; d_student or d_cook with
+ * d_A; p < 1 or lda < p with d_A.
+ * Waits where lsq_dense_qr_covariance waits; the launches behind the rank are stream-ordered. */
+int lsq_dense_qr_leverage(lsq_solver *s, lsq_mat *J, const double *d_A, int p, int lda, const double *d_f, double *d_q,
+                          double *d_se, double *d_student, double *d_cook, double *h_s2, int *h_info);
+/* The same for a block-diagonal Jacobian (lsq_blockdiag_create, nb <= 64): B independent fits, one per block, in one pass --
+ * the handle and the limits of lsq_solver_covariance.  `s` is an LSQ_CHOLESKY solver created on J, either for_lm.  A
+ * column-scaled handle means J S.  Outputs (device; any may be NULL, not all): d_h, d_se, d_student, d_cook: m = B*mb doubles
+ * in row order; d_s2: B doubles, s_b^2 = sum(f_b.^2) / (mb - nb) over the block's own rows, summed in lsq_solver_covariance's
+ * fixed order.  The lines above hold per block with s2 = s_b^2 and n = nb.  d_f: NULL (then only d_h may be asked for) or the
+ * residual.  The factor is a CholeskyQR2: J_b'J_b = U_b'U_b, the unpivoted factorisation of lsq_solver_covariance, then
+ * z_i = inv(U_b)' a_i, sum z z' = U2'U2 and h_i = ||inv(U2)' z_i||^2 -- three passes over the values, every sum in index order --
+ * so that the leverages keep the accuracy of a QR (cond(J_b) u, not cond(J_b)^2 u) wherever the first factorisation succeeds.
+ * h_info: NULL or B host ints, entry b = 0 or the 1-based column at which block b's factorisation
+ * meets a pivot that is not positive: such a block gets NaN in all of its mb rows of every output and in d_s2[b], the other
+ * blocks are unaffected and the call returns LSQ_OK.  Block b's bits do not depend on B, on the other blocks or on the run.
+ * LSQ_EARG with a message that names the alternative: a bordered, dense, CSC or operator handle; a solver of another kind or
+ * shape; every output NULL; d_f with mb <= nb; d_se, d_student, d_cook or d_s2 without d_f.
+ * Stream-ordered; synchronises only to return h_info.  New rows on this handle are not offered. */
+int lsq_solver_leverage(lsq_solver *s, lsq_mat *J, const double *d_f, double *d_h, double *d_se, double *d_student,
+                        double *d_cook, double *d_s2, int *h_info);
 
 /* The fast paths above that rely on co-resident workgroups (one-launch Cholesky, pipelined triangular solves, the QR panel's slab
  * exchange + pipelined certified solve) wait with a bound; a wait that gives up makes the solve repeat itself on the

@@ -987,6 +987,54 @@ class AllocatedSolver:
         return BorderedCovariance(B, nb, ng, dcov.get() if cov else None, dse.get() if stderr else None,
                                   dcr.get() if cross else None, rank=int(info[1]))
 
+    def dense_qr_leverage(self, f=None, A=None):
+        """lsq_dense_qr_leverage at the values the dense J holds now, from the QR() factor of this solver: a Leverage.
+        A=None: the rows of J, `.q` = `.h` the m leverages; with the residual `f` (DeviceVector or m host values) also `.se`,
+        `.studentized`, `.cook` and `.s2`.  A: p new rows (a p x n array, or n values for one row) in the parameter space the
+        handle means: `.q` the p quadratic forms a' inv(J'J) a and, with `f`, `.se` = sqrt(s2 q), the standard error of the
+        prediction: the confidence band is y^ +- t * se.  A rank-deficient J raises RankDeficientException."""
+        J = self.J
+        dense = not getattr(J, "sparse", True)
+        m, n = (J.m, J.n) if dense else (0, 0)      # (any other handle is refused by the library, with its message)
+        df = f if (f is None or hasattr(f, "ptr")) else DeviceVector(J.ctx, J.m, f)
+        dA, p = None, 0
+        if A is not None:
+            A = np.asarray(A, dtype=np.float64)
+            A = A.reshape((1, -1)) if A.ndim == 1 else A
+            if A.ndim != 2 or A.shape[1] != J.n:
+                raise DimensionMismatch(_lib.EDIM, "A has shape %s, expected (p, %d)" % (A.shape, J.n))
+            p = A.shape[0]
+            dA = DeviceVector(J.ctx, A.size, np.asfortranarray(A).reshape(-1, order="F"))
+        rows = p if A is not None else m
+        own = A is None and f is not None
+        dq = DeviceVector(J.ctx, rows)
+        dse = DeviceVector(J.ctx, rows) if f is not None else None
+        dt = DeviceVector(J.ctx, rows) if own else None
+        dck = DeviceVector(J.ctx, rows) if own else None
+        s2, info = C.c_double(0.0), np.zeros(1, dtype=np.int32)
+        check(lib().lsq_dense_qr_leverage(self.h, J.h, _ptr(dA), p, p, _ptr(df), dq.ptr, _ptr(dse), _ptr(dt), _ptr(dck),
+                                          C.byref(s2) if f is not None else None, info.ctypes.data_as(_lib.c_ip)))
+        return Leverage(dq.get(), se=None if dse is None else dse.get(), studentized=None if dt is None else dt.get(),
+                        cook=None if dck is None else dck.get(), s2=s2.value if f is not None else None, rank=int(info[0]))
+
+    def leverage(self, f=None):
+        """lsq_solver_leverage at the values the block-diagonal J holds now, on this Cholesky() solver: a Leverage over all
+        B * mb rows with `.block(b)`; `.s2` the B per-block variances and `.info` per block 0 or the column at which its
+        factorisation failed (that block is NaN).  `f`: None (the leverages alone) or the residual."""
+        J = self.J
+        B, mb, _ = J.blockdiag if getattr(J, "blockdiag", None) is not None else (0, 0, 0)   # (else refused by the library)
+        df = f if (f is None or hasattr(f, "ptr")) else DeviceVector(J.ctx, J.m, f)
+        rows = B * mb
+        dh = DeviceVector(J.ctx, rows)
+        dse, dt, dck = [DeviceVector(J.ctx, rows) if f is not None else None for _ in range(3)]
+        ds2 = DeviceVector(J.ctx, B) if f is not None else None
+        info = np.zeros(max(B, 1), dtype=np.int32)
+        check(lib().lsq_solver_leverage(self.h, J.h, _ptr(df), dh.ptr, _ptr(dse), _ptr(dt), _ptr(dck), _ptr(ds2),
+                                        info.ctypes.data_as(_lib.c_ip)))
+        if f is None:
+            return Leverage(dh.get(), info=info[:B], nblocks=B, mb=mb)
+        return Leverage(dh.get(), se=dse.get(), studentized=dt.get(), cook=dck.get(), s2=ds2.get(), info=info[:B], nblocks=B, mb=mb)
+
     def stats(self):
         """lsq_solver_stats: give-ups of the co-residency fast paths and how many solves each stays paused."""
         g, p = (C.c_int * 4)(), (C.c_int * 4)()
@@ -1136,6 +1184,54 @@ def dense_qr_covariance(Jd, f=None, stderr=True):
     sv = AllocatedSolver(Jd, QR(), for_lm=False)
     try:
         return sv.dense_qr_covariance(f=f, stderr=stderr)
+    finally:
+        sv.free()
+
+
+class Leverage:
+    """What lsq_dense_qr_leverage and lsq_solver_leverage return, on the host: `.q` (alias `.h`) the quadratic forms
+    a' inv(J'J) a -- the leverages when the rows are J's own -- and, where the residual was given, `.se` the standard errors of
+    the predictions, `.studentized` the internally studentized residuals, `.cook` Cook's distances (the latter two for J's own
+    rows only) and `.s2` the residual variance (one value, or one per block); else None.  Dense: `.rank`, the rank the solve
+    decided.  Block-diagonal: `.info` per block 0 or the 1-based column at which its factorisation failed (such a block is
+    NaN), and `.block(b)` the same quantities for the mb rows of block b (views)."""
+
+    def __init__(self, q, se=None, studentized=None, cook=None, s2=None, rank=None, info=None, nblocks=0, mb=0):
+        self.q = np.asarray(q, dtype=np.float64)
+        self.se, self.studentized, self.cook = se, studentized, cook
+        self.s2, self.rank = s2, rank
+        self.info = None if info is None else np.asarray(info, dtype=np.int32)
+        self.nblocks, self.mb = int(nblocks), int(mb)
+
+    @property
+    def h(self):
+        return self.q
+
+    def block(self, b):
+        if not 0 <= b < self.nblocks:
+            raise IndexError("block %d of %d" % (b, self.nblocks))
+        sl = slice(b * self.mb, (b + 1) * self.mb)
+        cut = lambda v: None if v is None else v[sl]
+        return Leverage(self.q[sl], se=cut(self.se), studentized=cut(self.studentized), cook=cut(self.cook),
+                        s2=None if self.s2 is None else float(self.s2[b]), info=self.info[b:b + 1])
+
+
+def dense_qr_leverage(Jd, f=None, A=None):
+    """Leverages (A=None) or prediction variances at new rows A of a dense DeviceMatrix at the values it holds: creates a QR()
+    solver (for_lm=False) on it, calls AllocatedSolver.dense_qr_leverage and frees the solver."""
+    sv = AllocatedSolver(Jd, QR(), for_lm=False)
+    try:
+        return sv.dense_qr_leverage(f=f, A=A)
+    finally:
+        sv.free()
+
+
+def leverage(Jd, f=None):
+    """Leverages of the B independent fits of a block-diagonal DeviceMatrix at the values it holds: creates a Cholesky() solver
+    on it, calls AllocatedSolver.leverage and frees the solver."""
+    sv = AllocatedSolver(Jd, Cholesky(), for_lm=True)
+    try:
+        return sv.leverage(f=f)
     finally:
         sv.free()
 

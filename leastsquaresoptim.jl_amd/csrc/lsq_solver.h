@@ -136,6 +136,10 @@ struct lsq_solver {
     // (the same on a BorderedQR() solver: lsq_bordered_qr_covariance, lsq_cov_bordered.hip)
     int *d_cov_info = nullptr;
     double *d_cov_buf = nullptr;
+    // --- lsq_dense_qr_leverage / lsq_solver_leverage (lsq_leverage.hip), grown on demand: the quadratic forms q when the
+    // caller asks only for what is derived from them; block-diagonal handles: the B variances s_b^2 in front of them
+    double *d_lev_buf = nullptr;
+    size_t lev_cap = 0;
     // --- a dense Cholesky() solver (lsq_dense_solver_alloc) owned by this one, factoring a Gram matrix that is written into its
     // d_chol.  lsq_sparse_covariance on an LSMR() solver (lsq_cov_sparse.hip), created on first use: m, n of this one, J'J.
     // Schur() on a bordered handle (lsq_schur.hip; br_blocks > 0, d_info and d_work as above), created with the solver: n = ng,

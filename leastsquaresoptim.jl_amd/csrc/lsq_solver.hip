@@ -43,6 +43,7 @@ extern "C" int lsq_solver_destroy(lsq_solver *s) {
     if (s->kind == LSQ_LSMR) lsq_lsmr_free(s);
     else lsq_dense_solver_free(s);     // (also the block-diagonal solvers: all they own is d_info, freed there)
     hipFree(s->d_cov_info); hipFree(s->d_cov_buf);     // lsq_solver_covariance
+    hipFree(s->d_lev_buf);                             // lsq_dense_qr_leverage / lsq_solver_leverage
     if (s->inner) {                                // lsq_sparse_covariance, Schur(), BorderedQR()
         hipFree(s->inner->d_cov_buf);              // (lsq_bordered_qr_covariance: the inner QR()'s zero right-hand side)
         lsq_dense_solver_free(s->inner);
