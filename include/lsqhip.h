@@ -510,6 +510,40 @@ int lsq_dense_qr_leverage(lsq_solver *s, lsq_mat *J, const double *d_A, int p, i
  * Stream-ordered; synchronises only to return h_info.  New rows on this handle are not offered. */
 int lsq_solver_leverage(lsq_solver *s, lsq_mat *J, const double *d_f, double *d_h, double *d_se, double *d_student,
                         double *d_cook, double *d_s2, int *h_info);
+/* lsq_dense_qr_leverage for a bordered block-diagonal Jacobian J = [blkdiag(J_1 .. J_B) | C] (lsq_blockdiag_bordered_create), the
+ * Jacobian of a global fit, from the factor of LSQ_BORDERED_QR: which points of which data set drive the shared parameters, and
+ * the confidence band of curve b.  `s` is an LSQ_BORDERED_QR solver created on J (nb <= 64, any ng >= 1, for_lm = 1).  Neither
+ * J'J nor the n x n covariance is formed, so the condition number is not squared.  A column-scaled handle means J S.  No damping
+ * is involved; J, the new rows and d_f are not written.
+ *   d_Ab = d_Ag = NULL: the m = B*mb rows of J in row order, q_i = h_i; block, p, ldab and ldag are ignored.
+ *   d_Ab and d_Ag both non-NULL: p >= 1 new rows of block `block` (0 <= block < B) in the parameter space the handle means:
+ *   d_Ab their local parts, p x nb column-major with leading dimension ldab >= p, d_Ag their shared parts, p x ng with leading
+ *   dimension ldag >= p (device); there are p outputs.  d_student and d_cook must then be NULL.
+ *   d_f, d_q, d_se, d_student, d_cook, h_s2: as for lsq_dense_qr_leverage, line for line, with ONE variance
+ *   s2 = lsq_sumsq(f) / (m - n), m = B*mb, n = B*nb + ng, and that n in Cook's distance.
+ *   h_info: NULL or 2 ints, as for lsq_bordered_qr_covariance: h_info[0] 0 or the 1-based stacked column of a failing local,
+ *   h_info[1] the rank the inner QR() decided.
+ * With zero damping the elimination of LSQ_BORDERED_QR leaves per block Q_b'[J_b C_b] = [R_b W_b; 0 F_b], and F P = Q_g R_g is
+ * the solver's inner QR() (X_g = inv(R_g) as lsq_dense_qr_covariance forms it; the zeros of the elimination stand in the buffer
+ * lsq_bordered_qr_covariance allocates at its first call).  For a row with local part a_b and shared part c:
+ *       z = inv(R_b)' a_b      e = c - W_b' z      u = inv(R_g)' P' e      q = ||z||^2 + ||u||^2
+ * k_bl_local (lsq_lev_bordered.hip): one workgroup per (block, 64 rows), R_b and Z in LDS, a forward substitution per row,
+ * ||z||^2 summed in index order, E = C - Z W_b on the fp64 matrix unit with k in index order; for J's own rows E stands in the
+ * solver's workspace (the place of F, of which the inner QR() has its copy), for new rows in a solver-owned buffer grown on
+ * demand.  Then lsq_dense_qr_leverage's kernel on E with X_g and the inner pivots, one IEEE addition q = ||z||^2 + ||u||^2, and
+ * the derived lines above.  Row i's bits depend on row i and on the factor only: not on p, on where the row stands, on the
+ * other rows, on which outputs are asked for, on the run, or on lsq_debug_set(serial = 1); on a handle without a column scale
+ * a block's own rows passed as new rows give the bits of d_Ab = NULL.  No floating-point atomics.
+ * A failing local column or an inner rank < ng: LSQ_ERANK with lsq_bordered_qr_covariance's messages and h_info.  The outputs
+ * are then unspecified; the solver stays usable for solves, covariances and leverages, and a solve or a covariance after a
+ * leverage has the bits of one without it.
+ * LSQ_EARG, each with a message that names the alternative: a solver of another kind; a handle that is not bordered; a shape
+ * other than the solver's; m < n; every output NULL; d_f with m <= n; d_se, d_student, d_cook or h_s2 without d_f; d_student or
+ * d_cook with new rows; only one of d_Ab and d_Ag; block out of range; p < 1 or a leading dimension below p.
+ * Waits where lsq_bordered_qr_covariance waits; the launches behind that are stream-ordered. */
+int lsq_bordered_qr_leverage(lsq_solver *s, lsq_mat *J, int block, const double *d_Ab, int ldab, const double *d_Ag, int ldag,
+                             int p, const double *d_f, double *d_q, double *d_se, double *d_student, double *d_cook,
+                             double *h_s2, int *h_info);
 
 /* The fast paths above that rely on co-resident workgroups (one-launch Cholesky, pipelined triangular solves, the QR panel's slab
  * exchange + pipelined certified solve) wait with a bound; a wait that gives up makes the solve repeat itself on the

@@ -7,7 +7,7 @@ from .api import (axpy_, box_clip_, clamp_, copyto_, ediv_, fill_, first_nonfini
                   AllocatedSolver, BatchedResult, BlockDiagonal, Covariance, covariance, DenseCovariance, dense_covariance, dense_qr_covariance, sparse_covariance, BorderedCovariance, bordered_qr_covariance, sparse_gram, BlockQR, BorderedBlockDiagonal, BorderedQR, Cholesky, Schur, Context, PinnedBuffer, DeviceMatrix, DeviceOperator, DeviceVector, Dogleg, LSMR,
                   LeastSquaresProblem, LeastSquaresProblemAllocated, LeastSquaresResult, LevenbergMarquardt, OptimizationState, QR,
                   Loss, LOSSES, loss_transform, robust_twin,
-                  Leverage, leverage, dense_qr_leverage,
+                  Leverage, leverage, dense_qr_leverage, bordered_qr_leverage,
                   colsumabs2_, rowsumabs2_, converged, default_context, default_optimizer, default_solver,
                   fd_jacobian_, greedy_colouring, maxabs, maxabs_projected_gradient, mul_, norm, optimize, optimize_, optimize_batched_, set_exact, debug_set, debug_get, sumsq, wdot,
                   wnorm)

@@ -172,6 +172,7 @@ def lib():
         "lsq_sparse_covariance": (i, [vp, vp, vp, vp, vp, c_ip]),
         "lsq_dense_qr_leverage": (i, [vp, vp, vp, i, i, vp, vp, vp, vp, vp, c_dp, c_ip]),
         "lsq_solver_leverage": (i, [vp, vp, vp, vp, vp, vp, vp, vp, c_ip]),
+        "lsq_bordered_qr_leverage": (i, [vp, vp, i, vp, i, vp, i, i, vp, vp, vp, vp, vp, c_dp, c_ip]),
         "lsq_solver_stats": (i, [vp, c_ip, c_ip]),
         "lsq_ctx_fallback_stats": (i, [vp, c_ip]),
         "lsq_ctx_device_info": (i, [vp, c_ip, c_ip, C.c_char_p, i]),

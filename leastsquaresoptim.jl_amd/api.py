@@ -1035,6 +1035,49 @@ class AllocatedSolver:
             return Leverage(dh.get(), info=info[:B], nblocks=B, mb=mb)
         return Leverage(dh.get(), se=dse.get(), studentized=dt.get(), cook=dck.get(), s2=ds2.get(), info=info[:B], nblocks=B, mb=mb)
 
+    def bordered_qr_leverage(self, f=None, block=None, A_local=None, A_shared=None):
+        """lsq_bordered_qr_leverage at the values the bordered J holds now, from the factor of this BorderedQR() solver: a
+        Leverage with `.rank` (the inner QR()'s) and `.block(b)`.  A_local = A_shared = None: the B * mb rows of J, `.q` = `.h`
+        the leverages; with the residual `f` (DeviceVector or m host values) also `.se`, `.studentized`, `.cook` and `.s2` (one
+        variance, sum(f.^2) / (m - n)).  `block`, A_local (p x nb, or nb values for one row) and A_shared (p x ng): p new rows of
+        that block in the parameter space the handle means: `.q` the p quadratic forms and, with `f`, `.se` = sqrt(s2 q), the
+        standard error of the prediction.  A zero or non-finite local column, or a rank-deficient border, raises
+        RankDeficientException."""
+        J = self.J
+        B, mb, nb, ng = J.bordered if getattr(J, "bordered", None) is not None else (0, 0, 0, 0)   # (else refused by the library)
+        df = f if (f is None or hasattr(f, "ptr")) else DeviceVector(J.ctx, J.m, f)
+        fresh = A_local is not None or A_shared is not None
+        dAb = dAg = None
+        p = 0
+        if A_local is not None:
+            A_local = np.asarray(A_local, dtype=np.float64)
+            A_local = A_local.reshape((1, -1)) if A_local.ndim == 1 else A_local
+            if A_local.ndim != 2 or A_local.shape[1] != nb:
+                raise DimensionMismatch(_lib.EDIM, "A_local has shape %s, expected (p, %d)" % (A_local.shape, nb))
+            p = A_local.shape[0]
+            dAb = DeviceVector(J.ctx, A_local.size, np.asfortranarray(A_local).reshape(-1, order="F"))
+        if A_shared is not None:
+            A_shared = np.asarray(A_shared, dtype=np.float64)
+            A_shared = A_shared.reshape((1, -1)) if A_shared.ndim == 1 else A_shared
+            if A_shared.ndim != 2 or A_shared.shape[1] != ng or (A_local is not None and A_shared.shape[0] != p):
+                raise DimensionMismatch(_lib.EDIM, "A_shared has shape %s, expected (%s, %d)"
+                                        % (A_shared.shape, p if A_local is not None else "p", ng))
+            p = A_shared.shape[0]
+            dAg = DeviceVector(J.ctx, A_shared.size, np.asfortranarray(A_shared).reshape(-1, order="F"))
+        rows = p if fresh else B * mb
+        own = not fresh and f is not None
+        dq = DeviceVector(J.ctx, rows)
+        dse = DeviceVector(J.ctx, rows) if f is not None else None
+        dt = DeviceVector(J.ctx, rows) if own else None
+        dck = DeviceVector(J.ctx, rows) if own else None
+        s2, info = C.c_double(0.0), np.zeros(2, dtype=np.int32)
+        check(lib().lsq_bordered_qr_leverage(self.h, J.h, -1 if block is None else int(block), _ptr(dAb), p, _ptr(dAg), p, p,
+                                             _ptr(df), dq.ptr, _ptr(dse), _ptr(dt), _ptr(dck),
+                                             C.byref(s2) if f is not None else None, info.ctypes.data_as(_lib.c_ip)))
+        return Leverage(dq.get(), se=None if dse is None else dse.get(), studentized=None if dt is None else dt.get(),
+                        cook=None if dck is None else dck.get(), s2=s2.value if f is not None else None, rank=int(info[1]),
+                        nblocks=0 if fresh else B, mb=0 if fresh else mb)
+
     def stats(self):
         """lsq_solver_stats: give-ups of the co-residency fast paths and how many solves each stays paused."""
         g, p = (C.c_int * 4)(), (C.c_int * 4)()
@@ -1212,8 +1255,9 @@ class Leverage:
             raise IndexError("block %d of %d" % (b, self.nblocks))
         sl = slice(b * self.mb, (b + 1) * self.mb)
         cut = lambda v: None if v is None else v[sl]
-        return Leverage(self.q[sl], se=cut(self.se), studentized=cut(self.studentized), cook=cut(self.cook),
-                        s2=None if self.s2 is None else float(self.s2[b]), info=self.info[b:b + 1])
+        s2 = None if self.s2 is None else float(self.s2 if np.ndim(self.s2) == 0 else self.s2[b])    # (bordered: one variance)
+        return Leverage(self.q[sl], se=cut(self.se), studentized=cut(self.studentized), cook=cut(self.cook), s2=s2,
+                        rank=self.rank, info=None if self.info is None else self.info[b:b + 1])
 
 
 def dense_qr_leverage(Jd, f=None, A=None):
@@ -1232,6 +1276,16 @@ def leverage(Jd, f=None):
     sv = AllocatedSolver(Jd, Cholesky(), for_lm=True)
     try:
         return sv.leverage(f=f)
+    finally:
+        sv.free()
+
+
+def bordered_qr_leverage(Jd, f=None, block=None, A_local=None, A_shared=None):
+    """Leverages (no new rows) or prediction variances at new rows of one block of a bordered block-diagonal DeviceMatrix at the
+    values it holds: creates a BorderedQR() solver on it, calls AllocatedSolver.bordered_qr_leverage and frees the solver."""
+    sv = AllocatedSolver(Jd, BorderedQR(), for_lm=True)
+    try:
+        return sv.bordered_qr_leverage(f=f, block=block, A_local=A_local, A_shared=A_shared)
     finally:
         sv.free()
 

@@ -416,7 +416,7 @@ k_bd_lev(int B, int mb, int nb, const double *__restrict__ vals, const double *_
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static int lev_scratch(lsq_solver *s, size_t doubles, double **out) {
+int lsq_lev_scratch(lsq_solver *s, size_t doubles, double **out) {
     if (s->lev_cap < doubles) {
         if (s->d_lev_buf) {
             LSQ_HIP(hipStreamSynchronize(s->ctx->stream));
@@ -446,7 +446,7 @@ extern "C" int lsq_dense_qr_leverage(lsq_solver *s, lsq_mat *J, const double *d_
     }
     if (J->kind != LSQ_MAT_DENSE) {
         lsq_set_error("lsq_dense_qr_leverage: the Jacobian is not a dense handle (lsq_dense_create); block-diagonal handles "
-                      "have lsq_solver_leverage, bordered, CSC and operator handles are not offered");
+                      "have lsq_solver_leverage, bordered ones lsq_bordered_qr_leverage, CSC and operator handles are not offered");
         return LSQ_EARG;
     }
     if (J->m != s->m || J->n != s->n) {
@@ -502,7 +502,7 @@ extern "C" int lsq_dense_qr_leverage(lsq_solver *s, lsq_mat *J, const double *d_
     if (!d_q && !d_se && !d_student && !d_cook) return LSQ_OK;
     const int rows = d_A ? p : m;
     double *q = d_q;
-    if (!q) LSQ_TRY(lev_scratch(s, (size_t)rows, &q));
+    if (!q) LSQ_TRY(lsq_lev_scratch(s, (size_t)rows, &q));
     if (d_A) {
         LSQ_LAUNCH(k_lev_tall, dim3(lsq_div_up(rows, LV_T)), dim3(256), 0, c->stream, d_A, lda, rows, n, X, jp,
                    (const double *)nullptr, q);
@@ -548,7 +548,8 @@ extern "C" int lsq_solver_leverage(lsq_solver *s, lsq_mat *J, const double *d_f,
     }
     if (J->br_blocks) {
         lsq_set_error("lsq_solver_leverage: not built for a bordered block-diagonal handle (the shared columns couple the blocks); "
-                      "lsq_solver_covariance or lsq_bordered_qr_covariance give the parameter covariance there");
+                      "lsq_bordered_qr_leverage with a BorderedQR() solver gives the leverages there, lsq_solver_covariance or "
+                      "lsq_bordered_qr_covariance the parameter covariance");
         return LSQ_EARG;
     }
     if (J->bd_blocks == 0) {
@@ -586,7 +587,7 @@ extern "C" int lsq_solver_leverage(lsq_solver *s, lsq_mat *J, const double *d_f,
     double *h = d_h, *s2 = d_s2;
     if ((derived && (!h || !s2))) {
         double *buf = nullptr;
-        LSQ_TRY(lev_scratch(s, (size_t)B + (size_t)m, &buf));
+        LSQ_TRY(lsq_lev_scratch(s, (size_t)B + (size_t)m, &buf));
         if (!s2) s2 = buf;
         if (!h) h = buf + B;
     }

@@ -137,7 +137,8 @@ struct lsq_solver {
     int *d_cov_info = nullptr;
     double *d_cov_buf = nullptr;
     // --- lsq_dense_qr_leverage / lsq_solver_leverage (lsq_leverage.hip), grown on demand: the quadratic forms q when the
-    // caller asks only for what is derived from them; block-diagonal handles: the B variances s_b^2 in front of them
+    // caller asks only for what is derived from them; block-diagonal handles: the B variances s_b^2 in front of them;
+    // lsq_bordered_qr_leverage (lsq_lev_bordered.hip): ||z||^2 | ||u||^2 | q | for new rows their p x ng matrix E
     double *d_lev_buf = nullptr;
     size_t lev_cap = 0;
     // --- a dense Cholesky() solver (lsq_dense_solver_alloc) owned by this one, factoring a Gram matrix that is written into its
@@ -296,6 +297,16 @@ int lsq_dense_qr_cov_factor(lsq_solver *s, lsq_mat *J, const double **X, const i
 int lsq_dense_qr_cov_finish(lsq_solver *s, int n, const double *X, const int *jp, double s2, double *d_cov, double *d_stderr);
 struct LsqBdqView { double *R, *W, *F; };     // R_b (B nb x nb, rows) | W ((B nb) x ng, column-major) | F ((B mb) x ng) in d_work
 int lsq_borderedqr_eliminate(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, LsqBdqView *view);
+// implemented in lsq_leverage.hip: the solver's leverage scratch (d_lev_buf), grown to `doubles`; the hot path and the derived
+// outputs of lsq_dense_qr_leverage, which lsq_bordered_qr_leverage (lsq_lev_bordered.hip) launches on its own operands
+int lsq_lev_scratch(lsq_solver *s, size_t doubles, double **out);
+#ifdef __HIPCC__
+__global__ void k_lev_tall(const double *__restrict__ A, int lda, int p, int n, const double *__restrict__ X,
+                           const int *__restrict__ jp, const double *__restrict__ scale, double *__restrict__ q);
+__global__ void k_lev_diag(long long m, const double *__restrict__ q, const double *__restrict__ f, double s2,
+                           const double *__restrict__ s2b, int mb, double ncook, double *__restrict__ se, double *__restrict__ t,
+                           double *__restrict__ cook);
+#endif
 // implemented in lsq_blockqr.hip
 int lsq_blockqr_solver_alloc(lsq_solver *s, const lsq_mat *J);
 int lsq_blockqr_solve(lsq_solver *s, lsq_mat *J, const double *d_y, const double *d_damp, double *d_x, int *nmul);
